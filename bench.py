@@ -10,12 +10,17 @@ the parameter dimension P = 784·10 + 10 = 7850.
 Workload (BASELINE config 2 at N=1, config 4 at N=8): synthetic MNIST-shaped data
 (X = rand(60000, 784), one-hot labels over 10 classes), batch 500, α = 0.01, ε = 1e-3,
 λ = 1e-2 (E[L] ≈ 10.5), zero start, one chain per GPU, float64 (the reference's dtype),
-device Philox noise.  Ranks run independent chains (no communication while sampling); after the
-timed region an untimed diagnostics run returns every step's state, and one all-gather (RCCL) moves
+device Philox noise.  Ranks run independent chains (no communication while sampling); with --full, after
+the timed region an untimed diagnostics run returns every step's state, and one all-gather (RCCL) moves
 each chain's per-parameter Welford mean / M2 and thinned trace to rank 0 for R̂ / split-R̂ / ESS.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps,
+the JSON line.  --full adds everything else the line can report (the untimed diagnostics run and its
+all-gather, the predicted scaling, the chain-batched / MLP / config-5 legs and the CPU baselines);
+--dump-outputs DIR writes the arrays the timed path returned for its last call (DIR/<name>.npy).
 """
 import argparse
 import io
@@ -49,19 +54,30 @@ def parse():
     ap.add_argument("--warmup", type=int, default=120)
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--path", choices=["auto", "kernels", "persistent"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the untimed diagnostics steps and their "
+                         "all-gather, the predicted scaling, the secondary legs and the CPU baselines "
+                         "(the four options below apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call returned (chain state after "
+                         "the last step, per-step accept probability / accepted / log-likelihood / energies / "
+                         "path length) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="CPU-baseline time budget per baseline (0 = skip)")
+                    help="with --full: CPU-baseline time budget per baseline (0 = skip)")
     ap.add_argument("--batched-chains", type=int, default=8192,
-                    help="chains per GPU of the secondary chain-batched measurement (0 = skip); the line also "
-                         "reports 2048 chains (round 2's operating point) as a sweep point")
+                    help="with --full: chains per GPU of the secondary chain-batched measurement (0 = skip); the "
+                         "line also reports 2048 chains (round 2's operating point) as a sweep point")
     ap.add_argument("--mlp-steps", type=int, default=40,
-                    help="SGHMC steps of the secondary config-3 MLP measurement (0 = skip)")
+                    help="with --full: SGHMC steps of the secondary config-3 MLP measurement (0 = skip)")
     ap.add_argument("--sgld-steps", type=int, default=400,
-                    help="SGLD steps of the secondary config-5 (D=2048, K=38) measurement (0 = skip)")
+                    help="with --full: SGLD steps of the secondary config-5 (D=2048, K=38) measurement (0 = skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: ranks rendezvous over gloo, reduce a dummy count "
                          "and rank 0 prints the JSON line shape (tests/test_bench_launch.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                    # a plain run: the headline only
+        args.cpu_seconds, args.batched_chains, args.mlp_steps, args.sgld_steps = 0.0, 0, 0, 0
+    return args
 
 
 def aggregate_ranks(per_rank, P_dim=P):
@@ -510,6 +526,48 @@ def warmup_calls(warmup, chunk):
     return calls
 
 
+def dump_outputs(dst, rank, state, res):
+    """--dump-outputs: what the timed path handed back for its last call, one .npy per array — the chain
+    state after the last timed step (the tensors every call updates in place) and the per-step outputs of
+    that call, whose last row is the last timed step.  The state keeps the run's dtype, the rest is
+    float64 (a few kB in all).  Rank 0 writes <name>.npy, rank r > 0 <name>_rank<r>.npy (its own chain)."""
+    os.makedirs(dst, exist_ok=True)
+    arrays = {"weights": state["weights"].detach().cpu().numpy(), "bias": state["bias"].detach().cpu().numpy(),
+              "accept_prob": res.A, "accepted": res.accepted, "log_likelihood": res.ll, "energies": res.E,
+              "path_length": res.L}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(dst, name + (".npy" if rank == 0 else "_rank%d.npy" % rank)), a)
+
+
+def diagnostics_run(args, parallel, s, run, lls, rank, dev):
+    """--full: cross-chain diagnostics (untimed, after the timed region).  DIAG_STEPS more steps of the same
+    chain return the state after every step (out_trace); per-parameter Welford mean / M2 and a thinned
+    trace of every chain travel in ONE all-gather (RCCL over xGMI through libhmcx's
+    hmcx_allgather_chain_stats, parallel.py); rank 0 reports R̂, split-R̂ and ESS per parameter.  The
+    timed steps' log-likelihood trace is gathered too.  Returns (per-parameter summary, ll diagnostics)."""
+    chunk = N_DATA // B
+    s.record_steps = True
+    wf = parallel.Welford((1, P))
+    thin = []
+    done = 0
+    while done < DIAG_STEPS:
+        n = min(chunk, DIAG_STEPS - done)
+        st = run(n, args.warmup + args.steps + done).steps        # [n, 1, P]
+        wf.update(st.transpose(1, 0, 2))
+        thin.append(st[DIAG_THIN - 1::DIAG_THIN, 0])
+        done += n
+    s.record_steps = False
+    # R̂ / split-R̂ / ESS per parameter on the device, where the all-gather left the summaries
+    n_draws, means, M2, tr = parallel.gather_summaries(wf, np.concatenate(thin)[None], device=dev, keep_device=True)
+    diag_par = parallel.summary_diagnostics_device(n_draws, means, M2, tr) if rank == 0 else None
+    trace = np.concatenate(lls)[None, :, None]       # [1 chain, T, 1]
+    allt = parallel.gather_traces(trace, device=dev)
+    diag = parallel.chain_diagnostics(allt) if allt.shape[1] >= 4 else {"rhat": np.nan, "ess": np.nan}
+    return diag_par, diag
+
+
 def bench(args, parallel):
     import torch
     rank, world, local = parallel.init()
@@ -610,29 +668,12 @@ def bench(args, parallel):
     ranks = aggregate_ranks(per_rank)
     ranks["per_rank_kernel_ms"] = [r["kernel_ms"] for r in per_rank]
     rec = {"headline": recovery_delta(rec0)}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, state, res)
 
-    # cross-chain diagnostics (untimed, after the timed region): DIAG_STEPS more steps of the same
-    # chain return the state after every step (out_trace); per-parameter Welford mean / M2 and a
-    # thinned trace of every chain travel in ONE all-gather (RCCL over xGMI through libhmcx's
-    # hmcx_allgather_chain_stats, parallel.py); rank 0 reports R̂,
-    # split-R̂ and ESS per parameter.  The timed steps' log-likelihood trace is gathered too.
-    s.record_steps = True
-    wf = parallel.Welford((1, P))
-    thin = []
-    done = 0
-    while done < DIAG_STEPS:
-        n = min(CHUNK, DIAG_STEPS - done)
-        st = run(n, args.warmup + args.steps + done).steps        # [n, 1, P]
-        wf.update(st.transpose(1, 0, 2))
-        thin.append(st[DIAG_THIN - 1::DIAG_THIN, 0])
-        done += n
-    s.record_steps = False
-    # R̂ / split-R̂ / ESS per parameter on the device, where the all-gather left the summaries
-    n_draws, means, M2, tr = parallel.gather_summaries(wf, np.concatenate(thin)[None], device=dev, keep_device=True)
-    diag_par = parallel.summary_diagnostics_device(n_draws, means, M2, tr) if rank == 0 else None
-    trace = np.concatenate(lls)[None, :, None]       # [1 chain, T, 1]
-    allt = parallel.gather_traces(trace, device=dev)
-    diag = parallel.chain_diagnostics(allt) if allt.shape[1] >= 4 else {"rhat": np.nan, "ess": np.nan}
+    diag_par = diag = None
+    if args.full:
+        diag_par, diag = diagnostics_run(args, parallel, s, run, lls, rank, dev)
 
     batched = None
     if args.batched_chains > 0:
@@ -666,7 +707,7 @@ def bench(args, parallel):
     recov = {leg: sum(sum(r[leg].values()) for r in rec_all) for leg in rec}
     parallel.barrier()
     if rank == 0:
-        ranks["predicted"] = predicted_scaling(args.warmup, args.steps, calls_per_rank=n_calls)
+        ranks["predicted"] = predicted_scaling(args.warmup, args.steps, calls_per_rank=n_calls) if args.full else None
         report(args, world, value, t_max, lf_total, lf_local, n_calls, kern_ms, kern_n, diag_par, diag,
                batched, mlp_out, v_out, X, Y, ranks, recov)
     # closing barrier: every rank waits here until rank 0 has run its CPU baselines and printed, so the
@@ -726,7 +767,9 @@ def report(args, world, value, t_max, lf_total, lf_local, n_calls, kern_ms, kern
                      else "kernel-per-phase sequence of each call (%d call(s) of <= %d steps)" % (n_calls, CHUNK),
                      "launch_ms": launch_ms, "flop_per_launch": flop_per_launch, "calls": n_calls,
                      "leapfrogs_per_launch": lf_local / n_calls},
-        "diagnostics": {"per_parameter": diag_par,
+        "full": bool(args.full),
+        "diagnostics": None if diag is None else {
+                        "per_parameter": diag_par,
                         "source": "%d untimed steps after the timed region, state after every step; Welford "
                                   "mean/M2 per parameter and every %dth draw, one all_gather" % (DIAG_STEPS, DIAG_THIN),
                         "note": "burn-in, not a convergence check: the chains start at zero (2.-MNIST.ipynb) and "

@@ -58,7 +58,7 @@ def test_bench_world1_through_rccl():
     env = dict(os.environ, HMCX_DIST_FORCE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "1",
-           "--steps", "5", "--warmup", "2", "--cpu-seconds", "0", "--batched-chains", "0",
+           "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "0", "--batched-chains", "0",
            "--mlp-steps", "0", "--sgld-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -76,8 +76,8 @@ def test_bench_self_launch_two_ranks_shared_gpu():
     one-GPU box both share cuda:0 (HMCX_BENCH_SHARED_GPU) and reduce over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HMCX_BENCH_SHARED_GPU="1", HMCX_DIST_BACKEND="gloo")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--cpu-seconds", "0",
-           "--batched-chains", "0", "--mlp-steps", "0", "--sgld-steps", "0"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
+           "--cpu-seconds", "0", "--batched-chains", "0", "--mlp-steps", "0", "--sgld-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,7 +96,7 @@ def test_bench_four_ranks_shared_gpu_default_legs():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HMCX_BENCH_SHARED_GPU="1", HMCX_DIST_BACKEND="gloo")
     cmd = [sys.executable, "bench.py", "--gpus", "4", "--path", "kernels", "--steps", "20", "--warmup", "5",
-           "--cpu-seconds", "1"]
+           "--full", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -119,8 +119,8 @@ def test_bench_torchrun_two_ranks_shared_gpu():
     env.update(HMCX_BENCH_SHARED_GPU="1", HMCX_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2", "--path", "kernels",
-           "--steps", "5", "--warmup", "2", "--cpu-seconds", "0", "--batched-chains", "0", "--mlp-steps", "0",
-           "--sgld-steps", "0"]
+           "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "0", "--batched-chains", "0",
+           "--mlp-steps", "0", "--sgld-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -9,13 +9,14 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -1 gpurun_out/pytest_r05c.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/smoke_r05c.log 2>&1 || { tail gpurun_out/smoke_r05c.log; exit 1; }
 tail -1 gpurun_out/smoke_r05c.log
-timeout -k 10 400 python bench.py > gpurun_out/bench_default_r05c.json 2> gpurun_out/bench_default_r05c.err || { echo bench failed; tail gpurun_out/bench_default_r05c.err; exit 1; }
-python3 -c "import json; d=json.load(open('gpurun_out/bench_default_r05c.json')); print('default', d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'], d['chain_batched']['sweep'], d['mlp']['roofline']['frac'], d['plantvillage_sgld']['us_per_step'], d['recoveries'])"
+O=${BENCH_OUT:-$(pwd)/bench_out}; mkdir -p $O     # where the bench lines of this script go
+timeout -k 10 400 python bench.py --full > $O/bench_default_r05c.json 2> $O/bench_default_r05c.err || { echo bench failed; tail $O/bench_default_r05c.err; exit 1; }
+python3 -c "import json; d=json.load(open('$O/bench_default_r05c.json')); print('default', d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'], d['chain_batched']['sweep'], d['mlp']['roofline']['frac'], d['plantvillage_sgld']['us_per_step'], d['recoveries'])"
 for rep in 1 2 3; do
-  HMCX_BENCH_DEBUG=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_s20_r05c_$rep.json 2> gpurun_out/bench_s20_r05c_$rep.err || { echo bench s20 failed; tail gpurun_out/bench_s20_r05c_$rep.err; exit 1; }
-  python3 -c "import json; d=json.load(open('gpurun_out/bench_s20_r05c_$rep.json')); print('s20', d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'])"
+  HMCX_BENCH_DEBUG=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_s20_r05c_$rep.json 2> $O/bench_s20_r05c_$rep.err || { echo bench s20 failed; tail $O/bench_s20_r05c_$rep.err; exit 1; }
+  python3 -c "import json; d=json.load(open('$O/bench_s20_r05c_$rep.json')); print('s20', d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'])"
 done
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_r05c -o run --output-format csv -- python3 $R/bench.py > $R/gpurun_out/bench_prof_r05c.json 2> $R/gpurun_out/prof_r05c.err || { tail -5 $R/gpurun_out/prof_r05c.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_r05c -o run --output-format csv -- python3 $R/bench.py --full > $O/bench_prof_r05c.json 2> $O/prof_r05c.err || { tail -5 $O/prof_r05c.err; exit 1; }
 echo prof done
 cd $R && TAG=r05c bash tools/gpu_pmc_headline.sh && echo pmc done

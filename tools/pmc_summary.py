@@ -8,7 +8,7 @@ HBM/fabric bytes per launch = 2·FETCH_SIZE + WRITE_SIZE (kB units; MI355X_MICRO
 FETCH_SIZE counts half the bytes of 16-byte-per-lane reads, WRITE_SIZE is exact for 16-byte stores;
 both include Infinity-Cache hits).  The bench JSON of the profiled run says how many timed calls it
 made (roofline.calls) and how many leapfrogs they ran: the timed launches are the `calls` dispatches
-after the warm-up ones (bench.py runs warm-up, timed, then the untimed diagnostics calls), and their
+after the warm-up ones (bench.py runs warm-up, timed, then with --full the untimed diagnostics calls), and their
 bytes ÷ their leapfrogs is the per-leapfrog figure bench.py scales.
 """
 import csv
