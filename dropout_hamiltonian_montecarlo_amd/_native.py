@@ -105,7 +105,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_sgld_run", "hmcx_hmc_mvn_run", "hmcx_mlp_masks", "hmcx_mlp_grad", "hmcx_mlp_loss",
            "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_axpy", "hmcx_mvn_eval",
-           "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
+           "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics")
 
@@ -157,6 +157,8 @@ def load_library():
         if hasattr(lib, "hmcx_get_recoveries"):        # absent in older builds loaded for A/B runs
             lib.hmcx_get_recoveries.argtypes = [c_void_p, c_i64p]
             lib.hmcx_note_recovery.argtypes = [c_void_p, c_int]
+        if hasattr(lib, "hmcx_get_mlp_forward_counts"):
+            lib.hmcx_get_mlp_forward_counts.argtypes = [c_void_p, c_i64p]
         lib.hmcx_host_wait.argtypes = [c_void_p, c_void_p]
         lib.hmcx_philox_schedule.argtypes = [ctypes.c_uint64, ctypes.c_uint32, c_int, ctypes.c_uint32, c_int,
                                              c_double, c_dblp, c_dblp, c_i32p, c_dblp]
@@ -260,6 +262,15 @@ class Context:
     def note_recovery(self, kind):
         """Record a re-run the host layer performed (include/hmcx.h hmcx_note_recovery)."""
         self.check(self.lib.hmcx_note_recovery(self.h, self.RECOVERY_KINDS.index(kind)), "hmcx_note_recovery")
+
+    MLP_FORWARD_KINDS = ("fwdr", "batched", "single")        # include/hmcx.h hmcx_get_mlp_forward_counts
+
+    def mlp_forward_counts(self):
+        """Forward launches hmcx_mlp_sghmc_run has enqueued on this context, by kind (include/hmcx.h
+        hmcx_get_mlp_forward_counts): k_fwdr launches, batched k_mm fused forwards, single forwards."""
+        out = (ctypes.c_int64 * len(self.MLP_FORWARD_KINDS))()
+        self.check(self.lib.hmcx_get_mlp_forward_counts(self.h, out), "hmcx_get_mlp_forward_counts")
+        return dict(zip(self.MLP_FORWARD_KINDS, (int(v) for v in out)))
 
     mlp_fuse = True
 

@@ -566,6 +566,12 @@ int hmcx_get_recoveries(const hmcx_ctx* ctx, int64_t* counts) {
   return HMCX_OK;
 }
 
+int hmcx_get_mlp_forward_counts(const hmcx_ctx* ctx, int64_t counts[3]) {
+  if (!ctx || !counts) return HMCX_EINVAL;
+  for (int k = 0; k < 3; ++k) counts[k] = ctx->mlp_fwd_counts[k];
+  return HMCX_OK;
+}
+
 int hmcx_note_recovery(hmcx_ctx* ctx, int kind) {
   HMCX_GUARD_CTX(ctx);
   if (kind < 0 || kind >= HMCX_RECOVERY_KINDS) return set_error(ctx, HMCX_EINVAL, "unknown recovery kind");

@@ -68,6 +68,8 @@ struct hmcx_ctx {
   int* wide_abort_dev = nullptr;
   // re-runs after timed-out exchanges, by hmcx_recovery kind (hmcx_get_recoveries)
   int64_t recoveries[HMCX_RECOVERY_KINDS] = {0, 0, 0};
+  // forward launches enqueued by hmcx_mlp_sghmc_run, by kind (hmcx_get_mlp_forward_counts)
+  int64_t mlp_fwd_counts[3] = {0, 0, 0};
 };
 constexpr int ABORT_SLOTS = 64;
 constexpr int ABORT_WORDS = 4;       // abort_dev: the word, then workgroup / granule base / epoch of the first timeout

@@ -1732,6 +1732,7 @@ struct MlpNet {
   double* lpart_scr = nullptr;           // batched sampler: the sub-step's loss partials (unused output)
   int force_abort = -1, l23_count = 0;   // HMCX_MLP_FORCE_ABORT: the fused launch (0-based, per call) that aborts
   int l23_fit = 0;                       // fused grids that fit on the chip at once (occupancy × CUs / grid)
+  int64_t* fwd_counts = nullptr;         // the sampler's forward-launch counters (hmcx_get_mlp_forward_counts)
   unsigned long long* prof = nullptr;    // HMCX_MLP_PROF: stamps of every fused launch of the call
   int prof_cap = 0;
   int nvar(int v) const {
@@ -1842,6 +1843,7 @@ hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double
   const int B = net.B, nm = net.n_mid;
   hipError_t e;
   net.h1_valid = false;
+  if (net.fwd_counts) ++net.fwd_counts[2];
   if (!net.xw_valid) {                                        // xw = X·W1ᵀ
     MMArgs<T> a{};
     mm_set<T>(a, B, nm, net.n_in, net.X, net.n_in, 0, q[0], net.n_in, 1, net.xw, nm);
@@ -2050,6 +2052,7 @@ hipError_t mlp_forward_batch(MlpNet<T>& net, const SubStep<T>* ss, int np) {
   MMArgs<T> a;
   MMProbs<T> pr{};
   l23_build(net, sp, np, 0, a, pr);
+  if (net.fwd_counts) ++net.fwd_counts[1];
   return mm<T, MM_L23, 0, 1, OP_H1, OP_PLAIN, true>(net, a, &pr);
 }
 
@@ -2170,6 +2173,7 @@ bool fwdr_ok(const MlpNet<T>& net, const SubStep<T>* ss, int n) {
 template <typename T>
 hipError_t mlp_fwdr(MlpNet<T>& net, const SubStep<T>* const* ss, int np, const RbFwdArgs<T>* flags = nullptr) {
   if (np < 1 || np > FR_MAXP) return hipErrorInvalidValue;
+  if (net.fwd_counts) ++net.fwd_counts[0];
   RbFwdArgs<T> a{};
   if (flags) {                                                   // keep-flag rows: keep, n3, kr, seed, chain, step
     a.keep = flags->keep; a.n3 = flags->n3; a.kr = flags->kr; a.seed = flags->seed; a.chain = flags->chain;
@@ -2620,6 +2624,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
   MlpNet<T> net{};
   net_init(net, s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
   if (int rc0 = net_fuse<T>(ctx, net, MAXPROB)) return rc0;
+  net.fwd_counts = ctx->mlp_fwd_counts;
   const int mn = s->B * s->n_mid, n3 = 3 * mn;
   int off_v[6], dim[6], P = 0;                                // element offset of each variable in `order`
   {
@@ -2969,6 +2974,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
           MMArgs<T> a;
           MMProbs<T> pr{};
           l23_build(net, fa, na, 0, a, pr);
+          ctx->mlp_fwd_counts[1] += 2;                           // both launches carry batched fused forwards
           HMCX_HIP(ctx, (mm<T, MM_L23, 0, 1, OP_H1, OP_PLAIN, true>(net, a, &pr)));
           HMCX_HIP(ctx, mlp_l23_ga1<T>(net, fb, nb, ga, nga));
           // the W1 gradient with every pending bias / W3 update in its extra plane; then the next

@@ -457,6 +457,7 @@ class sghmc(sgmcmc):
                 t = self.trace[len(self.trace) - n_steps + s]
                 t['A'] = float(res.A[s])
                 t['accepted'] = bool(res.accepted[s])
+                t['E'] = res.E[s].tolist()             # (E_current, E_new) of the accept test
         return res
 
     # ------------------------------------------------------------------ single step (API parity)

@@ -231,6 +231,15 @@ enum hmcx_recovery {
 int hmcx_get_recoveries(const hmcx_ctx* ctx, int64_t* counts);
 int hmcx_note_recovery(hmcx_ctx* ctx, int kind);
 
+/* Which forward ran.  hmcx_mlp_sghmc_run picks the forward kernels per step from the shape, dtype and
+ * mask alignment of the call; the host counts the forward launches it enqueues, per context, so a test
+ * can require the path it means to cover (totals since hmcx_create):
+ *   counts[0]  k_fwdr launches (every forward of a batched leapfrog iteration in one launch; float32)
+ *   counts[1]  batched fused layer-2/3 launches of the k_mm family (several sub-steps per launch)
+ *   counts[2]  single forwards (one sub-step or one energy forward at a time)
+ * counts: host int64_t[3]. */
+int hmcx_get_mlp_forward_counts(const hmcx_ctx* ctx, int64_t counts[3]);
+
 /* Host-side Philox schedule of noise='philox' SGHMC steps (sghmc.py:25 path length, :36 accept
  * uniform), bit-identical to the device generator: for step s < n_steps and chain c < C
  *   L[s*C+c] = ceil(2·u_path·path_length / eps[s]),  n_iter = max(0, L − 1),  u = u_accept

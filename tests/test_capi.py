@@ -38,6 +38,20 @@ def test_argument_validation_without_device(nat):
     assert lib.hmcx_last_error(None) == b"null context"
 
 
+def test_mlp_forward_counts_abi(nat):
+    """hmcx_get_mlp_forward_counts exists, rejects null arguments without touching a device, and (with a
+    device) reports zeros on a fresh context."""
+    import torch
+    lib = nat.load_library()
+    out = (ctypes.c_int64 * 3)(7, 7, 7)
+    assert lib.hmcx_get_mlp_forward_counts(None, out) == -1
+    assert list(out) == [7, 7, 7]
+    if torch.cuda.is_available():
+        ctx = nat.Context(0)
+        assert lib.hmcx_get_mlp_forward_counts(ctx.h, None) == -1
+        assert ctx.mlp_forward_counts() == {"fwdr": 0, "batched": 0, "single": 0}
+
+
 _MIRRORS = [("SamplerArgs", "hmcx_sampler_args"), ("SgdArgs", "hmcx_sgd_args"), ("MvnArgs", "hmcx_hmc_mvn_args"),
             ("MlpParams", "hmcx_mlp_params"), ("MlpSghmcArgs", "hmcx_mlp_sghmc_args"), ("HmcArgs", "hmcx_hmc_args"),
             ("MlpLeapfrogArgs", "hmcx_mlp_leapfrog_args")]

@@ -109,51 +109,10 @@ def test_philox_masks_properties():
 
 
 # ----------------------------------------------------------------------------- SGHMC parity
-def _mask_stream(B, n_mid):
-    """Masks of forward f of global step k: sequential draws of RandomState(1000 + k)."""
-    cache = {}
-
-    def get(k, n):
-        rs = np.random.RandomState(1000 + k)
-        return np.stack([np.stack(om.dropout_masks(rs, B, n_mid, dtype=np.float64)) for _ in range(n)])
-
-    def one(k, f):
-        if k not in cache or cache[k].shape[0] <= f:
-            cache[k] = get(k, max(f + 1, 2 * (f + 1)))
-        return cache[k][f]
-    return get, one
-
-
-class _MaskedOracleMLP:
-    """oracle mlp whose grad / accept energies take injected masks in the sampler's call order."""
-
-    def __init__(self, inner, one):
-        self.inner, self.one = inner, one
-        self.k, self.f, self.in_step = 0, 0, False
-
-    def grad(self, par, **args):
-        m = self.one(self.k, self.f)
-        self.f += 1
-        return self.inner.grad(par, masks=list(m), **args)
-
-    def negative_log_posterior(self, par, **args):
-        if not self.in_step:
-            return self.inner.negative_log_posterior(par, masks=None, **args)
-        m = self.one(self.k, self.f)
-        self.f += 1
-        return self.inner.negative_log_posterior(par, masks=list(m), **args)
-
-    def log_likelihood(self, par, **args):
-        return self.inner.log_likelihood(par, masks=None, **args)
-
-
-class _OracleSghmc(osm.sghmc):
-    def step(self, state, momentum, rng, **args):
-        self.model.in_step, self.model.f = True, 0
-        out = super().step(state, momentum, rng, **args)
-        self.model.in_step = False
-        self.model.k += 1
-        return out
+# the mask stream and the masked oracle wrappers are shared with test_gpu_mlp_accept.py
+from _mlp_fixtures import MaskedOracleMLP as _MaskedOracleMLP  # noqa: E402
+from _mlp_fixtures import OracleSghmc as _OracleSghmc  # noqa: E402
+from _mlp_fixtures import mask_stream as _mask_stream  # noqa: E402
 
 
 @pytest.mark.parametrize("order", [list(om.MLP_PARAM_NAMES), ['/l3/b', '/l1/W', '/l2/b', '/l3/W', '/l1/b', '/l2/W']])
