@@ -759,6 +759,33 @@ int hmcx_hmc_run(hmcx_ctx* ctx, const hmcx_hmc_args* a) {
   return a->dtype == HMCX_F64 ? hmc_run_t<double>(ctx, a) : hmc_run_t<float>(ctx, a);
 }
 
+int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  if (a->model != HMCX_MODEL_SOFTMAX && a->model != HMCX_MODEL_LOGISTIC)
+    return set_error(ctx, HMCX_EINVAL, "hmc_chains: model must be HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC");
+  if (a->model == HMCX_MODEL_LOGISTIC && a->K != 1)
+    return set_error(ctx, HMCX_EINVAL, "hmc_chains: logistic needs K = 1");
+  if (a->C < 1) return set_error(ctx, HMCX_EINVAL, "hmc_chains: C < 1");
+  if (a->K > 64) return set_error(ctx, HMCX_EUNSUPPORTED, "hmc_chains: K > 64");
+  int rc = check_dims(ctx, a->dtype, a->B, a->D, a->K, a->C);
+  if (rc) return rc;
+  if (a->C > 65535) return set_error(ctx, HMCX_EUNSUPPORTED, "hmc_chains: more than 65535 chains");
+  if ((long long)a->D * a->K + a->K > 0x7fffffffLL) return set_error(ctx, HMCX_EUNSUPPORTED, "too many parameters");
+  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "n_steps < 0");
+  if (a->n_steps == 0) return HMCX_OK;
+  if (!a->X || !a->Y || !a->W || !a->b || !a->eps || !a->n_iter || !a->u_accept || !a->out_A || !a->out_accepted ||
+      !a->out_nlp)
+    return set_error(ctx, HMCX_EINVAL, "null pointer");
+  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
+    return set_error(ctx, HMCX_EINVAL, "BUFFER noise needs noise and noise_off");
+  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "bad noise_mode");
+  for (size_t i = 0; i < (size_t)a->n_steps * a->C; ++i)
+    if (a->n_iter[i] < 0) return set_error(ctx, HMCX_EINVAL, "n_iter < 0");
+  return a->dtype == HMCX_F64 ? hmc_chains_run_t<double>(ctx, a) : hmc_chains_run_t<float>(ctx, a);
+}
+
 int hmcx_mvn_eval(hmcx_ctx* ctx, int dim, int C, const double* mu, const double* prec, double nlp_const,
                   const double* x, double* g, double* nlp) {
   HMCX_GUARD_CTX(ctx);

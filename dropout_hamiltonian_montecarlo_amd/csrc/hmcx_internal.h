@@ -149,7 +149,7 @@ template <typename T> struct FwdArgs {
   int link;                  // Link (FWD_SGHMC: softmax only)
   T eps, clip_hi, clip_lo;
   int iter;
-  const int32_t* n_iter;
+  const int32_t* n_iter;     // FWD_SGHMC; FWD_GRAD of the chain-batched HMC run (iter = evaluation index)
   T* diff; T* colsum_part; double* ll_part; T* prob;
   // split-K forward (few, deep tiles): slab_mode 1 = write the XW partial of D slice blockIdx.z to
   // slab[z][B][N] and stop; 2 = skip the GEMM, XW = Σ_z slab[z] (fixed order), then the epilogue
@@ -164,9 +164,9 @@ template <typename T> struct GradArgs {
   T alpha, eps, one_minus_eps, noise_scale, m_half_eps;
   T gamma, lr;               // GRAD_SGD: momentum decay and step size (sgd.py:40)
   T half_eps;                // GRAD_HMC: 0.5·ε (hmc.py:50)
-  int hmc_flags;             // GRAD_HMC: HmcFlags
-  int iter;
-  const int32_t* n_iter;
+  int hmc_flags;             // GRAD_HMC: HmcFlags (one chain; ignored when n_iter is set)
+  int iter;                  // SGHMC: leapfrog iteration; chain-batched GRAD_HMC: gradient evaluation index
+  const int32_t* n_iter;     // device [C]; GRAD_HMC: set for the chain-batched run (flags per chain)
   const T* Wsrc; const T* bsrc;
   T* W; T* b; T* pW; T* pb; T* gW; T* gb;
   double* kin_part;   // SGHMC: [nDB][C] Σ pW² of the block at the chain's last iteration
@@ -237,6 +237,7 @@ template <typename T> int sgd_run_t(hmcx_ctx*, const hmcx_sgd_args*);
 template <typename T> int sumsq_t(hmcx_ctx*, const void*, int64_t, double*);
 template <typename T> int sghmc_run_t(hmcx_ctx*, const hmcx_sampler_args*);
 template <typename T> int hmc_run_t(hmcx_ctx*, const hmcx_hmc_args*);
+template <typename T> int hmc_chains_run_t(hmcx_ctx*, const hmcx_hmc_chains_args*);   // C chains, one call
 template <typename T> int axpy_t(hmcx_ctx*, int, int64_t, double, const void*, void*);
 bool sghmc_p2_selected(hmcx_ctx*, const hmcx_sampler_args*);   // hmcx_softmax.hip
 template <typename T> int sgld_run_t(hmcx_ctx*, const hmcx_sampler_args*);

@@ -31,8 +31,19 @@
 
 namespace hmcx {
 
+// Chain-batched full-batch HMC (hmc_chains_run_t): what follows gradient evaluation e of a chain whose
+// trajectory has n leapfrog iterations — the rule hmc_run_t applies on the host for its one chain.
+// 0 once the chain is past its last evaluation (e > 2n) or does not move (n = 0).
+__device__ __forceinline__ int hmc_chain_flags(int e, int n) {
+  if (n <= 0 || e > 2 * n) return 0;
+  if (e == 0) return HMC_HALF_W;                               // hmc.py:47 then iteration 0, weights
+  if (e & 1) return HMC_KICK_W | HMC_HALF_B;                   // after the weights' drift
+  return HMC_KICK_B | (e < 2 * n ? HMC_HALF_W : 0);            // after the bias' drift
+}
+
 // ------------------------------------------------------------------ forward (logits) kernel
-template <typename T, int NBLK, bool VEC, int NW>
+// HMCC: the FWD_GRAD launches of the chain-batched HMC run (a.iter = evaluation index, a.n_iter set)
+template <typename T, int NBLK, bool VEC, int NW, bool HMCC = false>
 __global__ __launch_bounds__(NW * 64) void k_fwd(FwdArgs<T> a) {
   using M = mfma16<T>;
   constexpr int NT = NBLK * 16, NTH = NW * 64, LD = NT + 1;
@@ -56,6 +67,11 @@ __global__ __launch_bounds__(NW * 64) void k_fwd(FwdArgs<T> a) {
   const bool sghmc = mode == FWD_SGHMC;
   const bool sig = a.link == LINK_SIGMOID;                 // logistic.py:43-55 (K = 1)
   const int nrow = min(16, a.B - m0);
+  if constexpr (HMCC) {                 // chain-batched HMC: a tile whose chains have all finished
+    bool any = false;
+    for (int cc = 0; cc < ncb; ++cc) any |= hmc_chain_flags(a.iter, a.n_iter[c0 + cc]) != 0;
+    if (!any) return;
+  }
 
   // ---- prefetch epilogue operands into registers (their latency overlaps the GEMM)
   T breg = T(0), bpreg = T(0);
@@ -276,7 +292,9 @@ __device__ inline double noise_at(const GradArgs<T>& a, int c, uint32_t e) {
 }
 
 // ------------------------------------------------------------------ gradient (Xᵀ·diff) kernel
-template <typename T, int NBLK, int NW>
+// HMCC: GRAD_HMC launches of the chain-batched HMC run — every chain derives its own sub-steps from
+// (a.iter, n_iter[c]) instead of a.hmc_flags
+template <typename T, int NBLK, int NW, bool HMCC = false>
 __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
   using M = mfma16<T>;
   constexpr int NT = NBLK * 16, NTH = NW * 64;
@@ -294,6 +312,12 @@ __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
   const int ncols = ncb * a.K;
   const int K = a.K;
   const int mode = a.mode;
+  constexpr bool hmcc = HMCC;
+  if constexpr (hmcc) {                 // a tile whose chains have all finished skips its GEMM
+    bool any = false;
+    for (int cc = 0; cc < ncb; ++cc) any |= hmc_chain_flags(a.iter, a.n_iter[c0 + cc]) != 0;
+    if (!any) return;
+  }
 
   // ---- prefetch the epilogue's per-element operands and noise (overlaps the GEMM)
   T wreg[EPT], preg[EPT], zreg[EPT];
@@ -305,6 +329,8 @@ __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
     const int d = d0 + i;
     ok[q] = e < 16 * NT && d < a.D && j < ncols;
     if (ok[q] && mode == GRAD_SGHMC) ok[q] = a.iter < a.n_iter[c0 + j / K];
+    if constexpr (hmcc)
+      if (ok[q]) ok[q] = (hmc_chain_flags(a.iter, a.n_iter[c0 + j / K]) & (HMC_KICK_W | HMC_HALF_W)) != 0;
     wreg[q] = preg[q] = zreg[q] = T(0);
     if (ok[q]) {
       const size_t idx = (size_t)d * a.N + n0 + j;
@@ -384,8 +410,9 @@ __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
       a.W[idx] = wreg[q] + m;                                             // sgd.py:41
     } else if (mode == GRAD_HMC) {
       T p = preg[q];
-      if (a.hmc_flags & HMC_KICK_W) p = p - a.eps * gr;                   // hmc.py:53
-      if (a.hmc_flags & HMC_HALF_W) {
+      const int fl = hmcc ? hmc_chain_flags(a.iter, a.n_iter[c0 + j / K]) : a.hmc_flags;
+      if (fl & HMC_KICK_W) p = p - a.eps * gr;                            // hmc.py:53
+      if (fl & HMC_HALF_W) {
         p = p - a.half_eps * gr;                                          // hmc.py:50
         a.W[idx] = wreg[q] + a.eps * p;                                   // hmc.py:51
       }
@@ -444,7 +471,8 @@ __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
     T pb_new = T(0);
     if (tid < ncols) {
       const int cc = tid / K, k = tid - cc * K, c = c0 + cc, col = n0 + tid;
-      const bool active = mode != GRAD_SGHMC || a.iter < a.n_iter[c];
+      const int fl = hmcc ? hmc_chain_flags(a.iter, a.n_iter[c]) : a.hmc_flags;
+      const bool active = hmcc ? (fl & (HMC_KICK_B | HMC_HALF_B)) != 0 : (mode != GRAD_SGHMC || a.iter < a.n_iter[c]);
       if (active) {
         T cs = csr[tid];
         for (int q = 1; q < G; ++q) cs += csr[q * NT + tid];
@@ -471,8 +499,8 @@ __global__ __launch_bounds__(NW * 64) void k_grad(GradArgs<T> a) {
           const T bb = a.b[col];
           const T gr = -(cs - a.alpha * bb);
           T p = a.pb[col];
-          if (a.hmc_flags & HMC_KICK_B) p = p - a.eps * gr;                 // hmc.py:53
-          if (a.hmc_flags & HMC_HALF_B) {
+          if (fl & HMC_KICK_B) p = p - a.eps * gr;                          // hmc.py:53
+          if (fl & HMC_HALF_B) {
             p = p - a.half_eps * gr;                                        // hmc.py:50
             a.b[col] = bb + a.eps * p;                                      // hmc.py:51
           }
@@ -678,8 +706,12 @@ static hipError_t launch_fwd(const FwdArgs<T>& a, const Tiling& t, hipStream_t s
   const int nz = a.slab_mode == 1 ? a.nslab : 1;
   dim3 grid(t.nRB, t.nCT, nz);
   const bool vec = (a.D % 4) == 0;
+  const bool hmcc = a.mode == FWD_GRAD && a.n_iter;   // chain-batched HMC
 #define HMCX_FWD(NB, NW)                                                                          \
-  if (vec) hipLaunchKernelGGL((k_fwd<T, NB, true, NW>), grid, dim3(NW * 64), 0, st, a);           \
+  if (hmcc) {                                                                                     \
+    if (vec) hipLaunchKernelGGL((k_fwd<T, NB, true, NW, true>), grid, dim3(NW * 64), 0, st, a);   \
+    else hipLaunchKernelGGL((k_fwd<T, NB, false, NW, true>), grid, dim3(NW * 64), 0, st, a);      \
+  } else if (vec) hipLaunchKernelGGL((k_fwd<T, NB, true, NW>), grid, dim3(NW * 64), 0, st, a);    \
   else hipLaunchKernelGGL((k_fwd<T, NB, false, NW>), grid, dim3(NW * 64), 0, st, a);
   // few, deep tiles (one chain, large D: config 5) split D over 8 waves instead of 4
   const bool deep = (size_t)t.nRB * t.nCT * nz <= 512 && a.D / nz >= 1024 && a.slab_mode != 2;
@@ -697,18 +729,17 @@ template <typename T>
 static hipError_t launch_grad(const GradArgs<T>& a, const Tiling& t, hipStream_t st) {
   dim3 grid(t.nDB, t.nCT);
   const bool deep = (size_t)t.nDB * t.nCT <= 512;
+  const bool hmcc = a.mode == GRAD_HMC && a.n_iter;   // chain-batched HMC
+#define HMCX_GRAD(NB, NW)                                                                         \
+  if (hmcc) hipLaunchKernelGGL((k_grad<T, NB, NW, true>), grid, dim3(NW * 64), 0, st, a);         \
+  else hipLaunchKernelGGL((k_grad<T, NB, NW>), grid, dim3(NW * 64), 0, st, a);
   switch (t.NBLK) {
-    case 1: hipLaunchKernelGGL((k_grad<T, 1, 8>), grid, dim3(512), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_grad<T, 2, 8>), grid, dim3(512), 0, st, a); break;
-    case 3:
-      if (deep) hipLaunchKernelGGL((k_grad<T, 3, 8>), grid, dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((k_grad<T, 3, 4>), grid, dim3(256), 0, st, a);
-      break;
-    default:
-      if (deep) hipLaunchKernelGGL((k_grad<T, 4, 8>), grid, dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((k_grad<T, 4, 4>), grid, dim3(256), 0, st, a);
-      break;
+    case 1: HMCX_GRAD(1, 8) break;
+    case 2: HMCX_GRAD(2, 8) break;
+    case 3: if (deep) { HMCX_GRAD(3, 8) } else { HMCX_GRAD(3, 4) } break;
+    default: if (deep) { HMCX_GRAD(4, 8) } else { HMCX_GRAD(4, 4) } break;
   }
+#undef HMCX_GRAD
   return hipGetLastError();
 }
 
@@ -1181,6 +1212,258 @@ int hmc_run_t(hmcx_ctx* ctx, const hmcx_hmc_args* s) {
     if (n > 0 || tr) {
       hipLaunchKernelGGL(k_hmc_commit<T>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st_, DK, K,
                          s->out_accepted + i, Wn, bn, W, b, tr);
+      HMCX_HIP(ctx, hipGetLastError());
+    }
+  }
+  if ((rc = gs.finish())) return rc;
+  return timing_end(ctx, ctx->stream);
+}
+
+// ------------------------------------------------------------------ full-batch HMC, C chains
+// hmc_multicore.py:22-38's intent (one hmc.sample per worker) as C chains of one call.  State, proposal
+// and momentum in the [D][C·K] / [C·K] layout of the SGHMC chains, so k_fwd / k_grad run all chains as
+// one GEMM (make_tiling packs min(64/K, C) chains per tile).  Per step:
+//   k_hmcc_init    p0, proposal := q, Σp0² partials                                  grid (nDB, C)
+//   max_c(1 + 2·n_iter[c]) × [k_fwd(FWD_GRAD) + k_grad(GRAD_HMC)] over all chains: each chain takes its
+//                  kicks/drifts from (evaluation index, n_iter[c]) — hmc_chain_flags — and a chain past
+//                  its last evaluation writes nothing; tiles of finished chains exit before the GEMM
+//   k_fwd(FWD_LL)  log-likelihood of the proposals
+//   k_hmcc_accept  energies, MH decision, carried HmcState per chain                 grid (C)
+//   k_hmcc_commit  q := proposal where accepted; trace rows                          grid (⌈P/256⌉, C)
+// Element i = d·K + k of chain c lives at (i / K)·N + c·K + i % K.
+template <typename T>
+struct HmcCInitArgs {
+  int D, K, C, N, P, nDB;
+  int noise_mode; const double* noise; const int64_t* noff;   // noff: device [C] row of this step
+  uint64_t seed; uint32_t chain0, step;
+  const T* W; const T* b; T* Wn; T* bn; T* pW; T* pb; T* mom;  // mom: [C][P] row of this step, or null
+  double* kin0_part;   // [nDB + 1][C]: Σ pW0² per block, then Σ pb0²
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_hmcc_init(HmcCInitArgs<T> a) {
+  __shared__ double ksh[256];
+  const int tid = threadIdx.x, K = a.K, c = blockIdx.y;
+  const int e0 = blockIdx.x * 16 * K, ne = min(16 * K, a.D * K - e0);
+  const int64_t noff = a.noise_mode == HMCX_NOISE_BUFFER ? a.noff[c] : 0;
+  double kin = 0.0;
+  for (int e = tid; e < ne; e += 256) {
+    const int i = e0 + e;
+    const size_t w = (size_t)(i / K) * a.N + c * K + i % K;
+    const T p = a.noise_mode == HMCX_NOISE_BUFFER ? (T)a.noise[noff + i]
+                                                  : philox_normal_t<T>(a.seed, a.chain0 + c, a.step, 0u, (uint32_t)i);
+    a.pW[w] = p;
+    a.Wn[w] = a.W[w];
+    if (a.mom) a.mom[(size_t)c * a.P + i] = p;
+    kin += (double)p * (double)p;
+  }
+  ksh[tid] = kin;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) ksh[tid] += ksh[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) a.kin0_part[(size_t)blockIdx.x * a.C + c] = ksh[0];
+  if (blockIdx.x == 0) {
+    __syncthreads();
+    double kb = 0.0;
+    if (tid < K) {
+      const int i = a.D * K + tid;
+      const T p = a.noise_mode == HMCX_NOISE_BUFFER ? (T)a.noise[noff + i]
+                                                    : philox_normal_t<T>(a.seed, a.chain0 + c, a.step, 0u, (uint32_t)i);
+      a.pb[c * K + tid] = p;
+      a.bn[c * K + tid] = a.b[c * K + tid];
+      if (a.mom) a.mom[(size_t)c * a.P + i] = p;
+      kb = (double)p * (double)p;
+    }
+    ksh[tid] = kb;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) ksh[tid] += ksh[tid + s];
+      __syncthreads();
+    }
+    if (tid == 0) a.kin0_part[(size_t)a.nDB * a.C + c] = ksh[0];
+  }
+}
+
+template <typename T>
+struct HmcCAcceptArgs {
+  int D, K, C, N, nRB, nDB, first, logistic;
+  const int32_t* n_iter; const double* u;                      // device [C] rows of this step
+  double neg_inv_n, log_prior, lpc0, lpc1, half_alpha;
+  const double* kin0_part; const double* ll0_part; const double* ll1_part;
+  const T* W; const T* b; const T* Wn; const T* bn; const T* pW; const T* pb;
+  HmcState* st;                                                // [C]
+  double* out_A; int32_t* out_acc; double* out_nlp; double* out_E;   // [C] rows of this step
+};
+
+// k_hmc_accept for chain blockIdx.x: the same sums in the same order, over the chain's columns.
+template <typename T>
+__global__ __launch_bounds__(256) void k_hmcc_accept(HmcCAcceptArgs<T> a) {
+  __shared__ double sh[256];
+  const int c = blockIdx.x, K = a.K, DK = a.D * K, C = a.C;
+  const int n_iter = a.n_iter[c];
+  const bool moved = n_iter > 0;
+  auto at = [&](const T* M, int i) { return (double)M[(size_t)(i / K) * a.N + c * K + i % K]; };
+  double ll0, sW0, sb0;
+  if (a.first) {
+    ll0 = block_sum256(a.nRB, [&](int i) { return a.ll0_part[(size_t)i * C + c]; }, sh);
+    sW0 = a.logistic ? block_sum256(DK, [&](int i) { const double v = at(a.W, i); return v * v; }, sh) : 0.0;
+    sb0 = a.logistic ? block_sum256(K, [&](int i) { const double v = (double)a.b[c * K + i]; return v * v; }, sh) : 0.0;
+  } else {
+    ll0 = a.st[c].ll; sW0 = a.st[c].sW; sb0 = a.st[c].sb;
+  }
+  const double S0W = block_sum256(a.nDB, [&](int i) { return a.kin0_part[(size_t)i * C + c]; }, sh);
+  double ll1 = ll0, sW1 = sW0, sb1 = sb0, S1W = 0.0, S1b = 0.0;
+  if (moved) {
+    ll1 = block_sum256(a.nRB, [&](int i) { return a.ll1_part[(size_t)i * C + c]; }, sh);
+    if (a.logistic) {
+      sW1 = block_sum256(DK, [&](int i) { const double v = at(a.Wn, i); return v * v; }, sh);
+      sb1 = block_sum256(K, [&](int i) { const double v = (double)a.bn[c * K + i]; return v * v; }, sh);
+    }
+    S1W = block_sum256(DK, [&](int i) { const double v = at(a.pW, i); return v * v; }, sh);
+    S1b = block_sum256(K, [&](int i) { const double v = (double)a.pb[c * K + i]; return v * v; }, sh);
+  }
+  if (threadIdx.x == 0) {
+    auto nlp = [&](double ll, double sW, double sb) {
+      double lp = a.log_prior;                                   // softmax.py:22-30 (constant)
+      if (a.logistic) lp = (((0.0 + a.lpc0) - a.half_alpha * sW) + a.lpc1) - a.half_alpha * sb;   // logistic.py:15-21
+      return a.neg_inv_n * (ll + lp);
+    };
+    const double K0 = (0.0 + 0.5 * S0W) + 0.5 * a.kin0_part[(size_t)a.nDB * C + c];
+    const double nlp0 = nlp(ll0, sW0, sb0);
+    const double Ecur = nlp0 + K0;
+    double Enew = Ecur, A = 1.0;
+    if (moved) {
+      const double K1 = (0.0 + 0.5 * S1W) + 0.5 * S1b;           // ½Σ(−p)² = ½Σp² (hmc.py:55-56)
+      Enew = nlp(ll1, sW1, sb1) + K1;
+      const double x = exp(Ecur - Enew);
+      A = (x < 1.0) ? x : 1.0;                                   // Python min(1, x): NaN → 1
+    }
+    const int acc = a.u[c] < A;
+    a.out_A[c] = A;
+    a.out_acc[c] = acc;
+    if (a.out_E) { a.out_E[2 * c] = Ecur; a.out_E[2 * c + 1] = Enew; }
+    HmcState s;
+    if (acc && moved) { s.ll = ll1; s.sW = sW1; s.sb = sb1; }
+    else { s.ll = ll0; s.sW = sW0; s.sb = sb0; }
+    a.st[c] = s;
+    a.out_nlp[c] = (acc && moved) ? nlp(ll1, sW1, sb1) : nlp0;
+  }
+}
+
+// q := proposal for the chains that accepted and moved; trace [C][P] row of the kept states.
+template <typename T>
+__global__ __launch_bounds__(256) void k_hmcc_commit(int D, int K, int N, const int32_t* acc, const int32_t* n_iter,
+                                                     const T* Wn, const T* bn, T* W, T* b, T* trace) {
+  const int c = blockIdx.y, DK = D * K, P = DK + K;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool take = acc[c] != 0 && n_iter[c] > 0;
+  if (!take && !trace) return;
+  if (i < DK) {
+    const size_t w = (size_t)(i / K) * N + c * K + i % K;
+    T v = W[w];
+    if (take) { v = Wn[w]; W[w] = v; }
+    if (trace) trace[(size_t)c * P + i] = v;
+  } else if (i < P) {
+    const int j = c * K + (i - DK);
+    T v = b[j];
+    if (take) { v = bn[j]; b[j] = v; }
+    if (trace) trace[(size_t)c * P + i] = v;
+  }
+}
+
+template <typename T>
+int hmc_chains_run_t(hmcx_ctx* ctx, const hmcx_hmc_chains_args* s) {
+  const int B = s->B, D = s->D, K = s->K, C = s->C, N = C * K, DK = D * K, P = DK + K;
+  const bool logistic = s->model == HMCX_MODEL_LOGISTIC;
+  const int link = logistic ? LINK_SIGMOID : LINK_SOFTMAX;
+  const Tiling t = make_tiling(B, D, K, C);
+  const size_t nsc = (size_t)s->n_steps * C;
+  Workspace ws(ctx);
+  T *Wn, *bn, *pW, *pb, *diff, *csp;
+  double *kin0, *ll0p, *ll1p, *d_u;
+  int32_t* d_niter;
+  int64_t* d_noff;
+  HmcState* st;
+  do {
+    ws.reset();
+    Wn = ws.take<T>((size_t)D * N); bn = ws.take<T>(N); pW = ws.take<T>((size_t)D * N); pb = ws.take<T>(N);
+    diff = ws.take<T>((size_t)B * N); csp = ws.take<T>((size_t)t.nRB * N);
+    kin0 = ws.take<double>((size_t)(t.nDB + 1) * C);
+    ll0p = ws.take<double>((size_t)t.nRB * C); ll1p = ws.take<double>((size_t)t.nRB * C);
+    st = ws.take<HmcState>(C);
+    d_niter = ws.take<int32_t>(nsc); d_u = ws.take<double>(nsc); d_noff = ws.take<int64_t>(nsc);
+  } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  begin_call(ctx);
+  int rc = upload(ctx, d_niter, s->n_iter, nsc * sizeof(int32_t));
+  if (rc) return rc;
+  if ((rc = upload(ctx, d_u, s->u_accept, nsc * sizeof(double)))) return rc;
+  if (s->noise_mode == HMCX_NOISE_BUFFER && (rc = upload(ctx, d_noff, s->noise_off, nsc * sizeof(int64_t))))
+    return rc;
+  if ((rc = timing_begin(ctx, ctx->stream))) return rc;
+  GraphScope gs(ctx);
+  hipStream_t st_ = ctx->stream;
+  T* W = (T*)s->W;
+  T* b = (T*)s->b;
+  // log-likelihood of the call's starting states (their nlp enters step 0's E_current)
+  {
+    FwdArgs<T> f = fwd_args<T>(s->X, s->Y, W, b, B, D, K, C, t, FWD_LL);
+    f.link = link;
+    f.ll_part = ll0p;
+    HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
+  }
+  for (int i = 0; i < s->n_steps; ++i) {
+    const double eps = s->eps[i];
+    const int32_t* niter = d_niter + (size_t)i * C;
+    int nmax = 0;
+    for (int c = 0; c < C; ++c) nmax = std::max(nmax, (int)s->n_iter[(size_t)i * C + c]);
+    HmcCInitArgs<T> ia{};
+    ia.D = D; ia.K = K; ia.C = C; ia.N = N; ia.P = P; ia.nDB = t.nDB;
+    ia.noise_mode = s->noise_mode; ia.noise = s->noise; ia.noff = d_noff + (size_t)i * C;
+    ia.seed = s->seed; ia.chain0 = s->chain0; ia.step = s->step_base + (uint32_t)i;
+    ia.W = W; ia.b = b; ia.Wn = Wn; ia.bn = bn; ia.pW = pW; ia.pb = pb;
+    ia.mom = s->out_mom ? (T*)s->out_mom + (size_t)i * C * P : nullptr;
+    ia.kin0_part = kin0;
+    hipLaunchKernelGGL(k_hmcc_init<T>, dim3(t.nDB, C), dim3(256), 0, st_, ia);
+    HMCX_HIP(ctx, hipGetLastError());
+    const int n_eval = nmax > 0 ? 1 + 2 * nmax : 0;
+    for (int e = 0; e < n_eval; ++e) {
+      FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, C, t, FWD_GRAD);
+      f.link = link;
+      f.diff = diff; f.colsum_part = csp;
+      f.iter = e; f.n_iter = niter;
+      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
+      GradArgs<T> g = grad_args<T>((const T*)s->X, diff, csp, B, D, K, C, t, GRAD_HMC, s->alpha);
+      g.eps = (T)eps; g.half_eps = (T)(0.5 * eps);
+      g.W = Wn; g.b = bn; g.pW = pW; g.pb = pb;
+      g.iter = e; g.n_iter = niter;
+      HMCX_HIP(ctx, launch_grad<T>(g, t, st_));
+    }
+    if (nmax > 0) {
+      FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, C, t, FWD_LL);
+      f.link = link;
+      f.ll_part = ll1p;
+      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
+    }
+    HmcCAcceptArgs<T> aa{};
+    aa.D = D; aa.K = K; aa.C = C; aa.N = N; aa.nRB = t.nRB; aa.nDB = t.nDB; aa.first = i == 0; aa.logistic = logistic;
+    aa.n_iter = niter; aa.u = d_u + (size_t)i * C;
+    aa.neg_inv_n = -1.0 / (double)B; aa.log_prior = s->log_prior;
+    aa.lpc0 = s->lp_const[0]; aa.lpc1 = s->lp_const[1]; aa.half_alpha = 0.5 * s->alpha;
+    aa.kin0_part = kin0; aa.ll0_part = ll0p; aa.ll1_part = ll1p;
+    aa.W = W; aa.b = b; aa.Wn = Wn; aa.bn = bn; aa.pW = pW; aa.pb = pb;
+    aa.st = st;
+    aa.out_A = s->out_A + (size_t)i * C; aa.out_acc = s->out_accepted + (size_t)i * C;
+    aa.out_nlp = s->out_nlp + (size_t)i * C;
+    aa.out_E = s->out_E ? s->out_E + (size_t)i * C * 2 : nullptr;
+    hipLaunchKernelGGL(k_hmcc_accept<T>, dim3(C), dim3(256), 0, st_, aa);
+    HMCX_HIP(ctx, hipGetLastError());
+    T* tr = s->out_trace ? (T*)s->out_trace + (size_t)i * C * P : nullptr;
+    if (nmax > 0 || tr) {
+      hipLaunchKernelGGL(k_hmcc_commit<T>, dim3((unsigned)((P + 255) / 256), C), dim3(256), 0, st_, D, K, N,
+                         s->out_accepted + (size_t)i * C, niter, Wn, bn, W, b, tr);
       HMCX_HIP(ctx, hipGetLastError());
     }
   }
@@ -1701,6 +1984,8 @@ template int sgd_run_t<float>(hmcx_ctx*, const hmcx_sgd_args*);
 template int sgd_run_t<double>(hmcx_ctx*, const hmcx_sgd_args*);
 template int hmc_run_t<float>(hmcx_ctx*, const hmcx_hmc_args*);
 template int hmc_run_t<double>(hmcx_ctx*, const hmcx_hmc_args*);
+template int hmc_chains_run_t<float>(hmcx_ctx*, const hmcx_hmc_chains_args*);
+template int hmc_chains_run_t<double>(hmcx_ctx*, const hmcx_hmc_chains_args*);
 template int axpy_t<float>(hmcx_ctx*, int, int64_t, double, const void*, void*);
 template int axpy_t<double>(hmcx_ctx*, int, int64_t, double, const void*, void*);
 template int sumsq_t<float>(hmcx_ctx*, const void*, int64_t, double*);

@@ -130,6 +130,20 @@ class hmc:
         X, y = m._xy(args)
         return X.contiguous(), y.contiguous()
 
+    def _linear_model_args(self, a, Xd, Yd, D, K, n_steps):
+        """The model part of hmcx_hmc_args / hmcx_hmc_chains_args (same field names in both)."""
+        m = self.model
+        a.dtype, a.model = m.code, nat.MODEL_LOGISTIC if m._hmcx_model == 'logistic' else nat.MODEL_SOFTMAX
+        a.B, a.D, a.K, a.n_steps = Xd.shape[0], D, K, n_steps
+        a.alpha = m.alpha
+        if m._hmcx_model == 'logistic':                                        # logistic.py:15-21
+            for i, var in enumerate(('weights', 'bias')):
+                dim = int(np.prod(np.shape(self.start[var])))
+                a.lp_const[i] = dim * 0.5 * np.log(m.hyper['alpha'] / (2 * np.pi))
+        else:
+            a.log_prior = m.log_prior_const([np.shape(self.start[v]) for v in self.start])
+        a.X, a.Y = ptr(Xd), ptr(Yd)
+
     def _linear_run(self, W, b, data, n_steps, rng, record):
         """n_steps HMC steps in one hmcx_hmc_run call.  Host work: the schedule in the reference's
         draw order (hmc.py:41 momentum from rng, :46 path length and :61 accept uniform from the
@@ -164,16 +178,7 @@ class hmc:
         tr = torch.empty((n_steps, P), dtype=m.dtype, device=dev) if record else None
         mo = torch.empty((n_steps, P), dtype=m.dtype, device=dev) if (record and noise is None) else None
         a = nat.HmcArgs()
-        a.dtype, a.model = m.code, nat.MODEL_LOGISTIC if m._hmcx_model == 'logistic' else nat.MODEL_SOFTMAX
-        a.B, a.D, a.K, a.n_steps = Xd.shape[0], D, K, n_steps
-        a.alpha = m.alpha
-        if m._hmcx_model == 'logistic':                                        # logistic.py:15-21
-            for i, var in enumerate(('weights', 'bias')):
-                dim = int(np.prod(np.shape(self.start[var])))
-                a.lp_const[i] = dim * 0.5 * np.log(m.hyper['alpha'] / (2 * np.pi))
-        else:
-            a.log_prior = m.log_prior_const([np.shape(self.start[v]) for v in self.start])
-        a.X, a.Y = ptr(Xd), ptr(Yd)
+        self._linear_model_args(a, Xd, Yd, D, K, n_steps)
         a.eps = eps.ctypes.data_as(nat.c_dblp)
         a.n_iter = n_iter.ctypes.data_as(nat.c_i32p)
         a.u_accept = u.ctypes.data_as(nat.c_dblp)

@@ -10,7 +10,10 @@
  *    and contiguous, unless the comment says "host".
  *  - C independent chains are stored chain-interleaved so the two gradient GEMMs see one
  *    [rows x C*K] matrix: weights W[D][C][K], bias b[C][K]  (C = 1 is exactly the
- *    reference's {'weights': [D,K], 'bias': [K]} layout).
+ *    reference's {'weights': [D,K], 'bias': [K]} layout).  The SGHMC / SGLD samplers
+ *    (hmcx_sampler_args) and the multi-chain full-batch HMC (hmcx_hmc_chains_args, the
+ *    reference's hmc_multicore) use it; per-(step, chain) schedules and outputs are indexed
+ *    s*C + c, Philox streams by chain id chain0 + c.
  *  - dtype: HMCX_F64 (the reference's float64) or HMCX_F32.
  *  - Return 0 on success or a negative hmcx_status; hmcx_last_error() has the message.
  *    No C++ exception crosses the ABI.  A context is bound to one device, owns its
@@ -324,6 +327,44 @@ typedef struct hmcx_hmc_args {
   void* out_mom;           /* device [n_steps][D*K+K] (dtype) or NULL: momentum drawn   */
 } hmcx_hmc_args;
 int hmcx_hmc_run(hmcx_ctx* ctx, const hmcx_hmc_args* a);
+
+/* C chains of the above in one call — the intent of hamiltonian/inference/cpu/hmc_multicore.py:22-38
+ * (one hmc.sample per worker; the reference's Pool.map omits `self`).  Every chain follows the
+ * semantics documented above hmcx_hmc_args; the chains share X, Y, eps and the launches.  State in the
+ * chain-interleaved layout of hmcx_sampler_args: W [D][C*K], b [C*K].  Schedules are per (step, chain),
+ * index s*C + c; a step launches max_c(1 + 2·n_iter[s][c]) gradient evaluations (k_fwd + k_grad over
+ * all chains), and each chain derives the kicks/drifts that follow evaluation e from (e, its own
+ * n_iter): a chain past its last evaluation (or with n_iter = 0: q kept, A = 1) writes nothing.
+ * BUFFER noise: P = D·K + K momentum normals per (step, chain) at noise_off[s*C + c] (weights
+ * row-major, then bias).  PHILOX: chain c draws Philox(seed, chain0 + c, step_base + s, slot 0, elem),
+ * the stream of a one-chain hmcx_hmc_run with chain = chain0 + c. */
+typedef struct hmcx_hmc_chains_args {
+  int dtype;
+  int model;               /* HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC                  */
+  int B, D, K, C, n_steps; /* B = N (full batch); C chains                              */
+  double alpha;
+  double log_prior;        /* softmax: constant log prior                               */
+  double lp_const[2];      /* logistic: dim·½·log(alpha/2π) of weights, bias            */
+  const void* X;
+  const void* Y;
+  const double* eps;       /* host [n_steps]                                            */
+  const int32_t* n_iter;   /* host [n_steps*C]  max(0, L − 1)                          */
+  const double* u_accept;  /* host [n_steps*C]                                          */
+  int noise_mode;
+  const double* noise;     /* device, BUFFER                                            */
+  const int64_t* noise_off;/* host [n_steps*C], BUFFER                                  */
+  uint64_t seed;
+  uint32_t chain0, step_base;
+  void* W;                 /* device [D][C*K] state, updated in place                   */
+  void* b;                 /* device [C*K]                                              */
+  double* out_A;           /* device [n_steps*C]                                        */
+  int32_t* out_accepted;   /* device [n_steps*C]                                        */
+  double* out_nlp;         /* device [n_steps*C]: nlp of the state kept after step s   */
+  double* out_E;           /* device [n_steps*C*2] (E_current, E_new) or NULL           */
+  void* out_trace;         /* device [n_steps][C][D*K+K] (dtype) or NULL: state after s */
+  void* out_mom;           /* device [n_steps][C][D*K+K] (dtype) or NULL: momentum drawn*/
+} hmcx_hmc_chains_args;
+int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a);
 
 /* Leapfrog arithmetic on device vectors of n elements (dtype), for hmc.step on models without a
  * fused entry (the MLP): mode 0  y −= a·x;  mode 1  y += a·x  (hmc.py:50-53, p −= ε·g, q += ε·p).
