@@ -521,6 +521,7 @@ int hmcx_destroy(hmcx_ctx* ctx) {
   if (ctx->wide_abort_dev) (void)hipFree(ctx->wide_abort_dev);
   if (ctx->zeros_dev) (void)hipFree(ctx->zeros_dev);
   if (ctx->gx_arena) (void)hipFree(ctx->gx_arena);
+  if (ctx->pred_ws) (void)hipFree(ctx->pred_ws);
   for (auto& g : ctx->graveyard) {
     (void)hipGraphExecDestroy(g.first);
     (void)hipEventDestroy(g.second);
@@ -1008,6 +1009,33 @@ int hmcx_mlp_hmc_leapfrog(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* a) {
     seen |= 1 << v;
   }
   return a->dtype == HMCX_F64 ? mlp_leapfrog_t<double>(ctx, a) : mlp_leapfrog_t<float>(ctx, a);
+}
+
+int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  int rc = check_mlp(ctx, a->dtype, a->N, a->n_in, a->n_mid, a->n_out);
+  if (rc) return rc;
+  if (a->S < 1 || a->T < 1) return set_error(ctx, HMCX_EINVAL, "mlp predictive: S and T must be >= 1");
+  const long long D = (long long)a->S * a->T;
+  if (D > 0x7fffffffLL || D * a->N > 0x7fffffffLL * 64)
+    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp predictive: too many draws");
+  if (!a->X || !mlp_par_ok(&a->par)) return set_error(ctx, HMCX_EINVAL, "mlp predictive: null pointer");
+  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
+      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp predictive: bad mask_mode");
+  if (a->mask_mode == HMCX_MLP_MASKS_NONE && a->T != 1)
+    return set_error(ctx, HMCX_EINVAL, "mlp predictive: without dropout every draw of a set is the same (T must be 1)");
+  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->masks)
+    return set_error(ctx, HMCX_EINVAL, "mlp predictive: FIXED masks required");
+  if (a->mask_mode == HMCX_MLP_MASKS_PHILOX && (unsigned long long)a->slot0 + (unsigned long long)D > 0x100000000ULL)
+    return set_error(ctx, HMCX_EINVAL, "mlp predictive: slot0 + S*T wraps 2^32");
+  if (!a->y && (a->out_lppd || a->out_draw_nll || a->out_draw_correct))
+    return set_error(ctx, HMCX_EINVAL, "mlp predictive: lppd / draw_nll / draw_correct need labels");
+  if (a->path < 0 || a->path > 2) return set_error(ctx, HMCX_EINVAL, "mlp predictive: path must be 0, 1 or 2");
+  if (a->path == 2 && !mlp_pred_fused_ok(ctx, a))
+    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp predictive: shape not eligible for the fused path");
+  return a->dtype == HMCX_F64 ? mlp_predictive_t<double>(ctx, a) : mlp_predictive_t<float>(ctx, a);
 }
 
 }  // extern "C"

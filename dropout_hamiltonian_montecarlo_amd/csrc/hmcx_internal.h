@@ -70,6 +70,10 @@ struct hmcx_ctx {
   int64_t recoveries[HMCX_RECOVERY_KINDS] = {0, 0, 0};
   // forward launches enqueued by hmcx_mlp_sghmc_run, by kind (hmcx_get_mlp_forward_counts)
   int64_t mlp_fwd_counts[3] = {0, 0, 0};
+  // hmcx_mlp_predictive's own buffers (logits, masks, accumulators, partials): apart from `ws`, which the
+  // per-draw forwards (mlp_loss_t) sub-allocate from offset 0 and may regrow
+  char* pred_ws = nullptr;
+  size_t pred_cap = 0;
 };
 constexpr int ABORT_SLOTS = 64;
 constexpr int ABORT_WORDS = 4;       // abort_dev: the word, then workgroup / granule base / epoch of the first timeout
@@ -252,5 +256,8 @@ template <typename T> int mlp_loss_t(hmcx_ctx*, const void*, const int32_t*, int
 template <typename T> int mlp_sghmc_t(hmcx_ctx*, const hmcx_mlp_sghmc_args*);
 template <typename T> int mlp_leapfrog_t(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
 template <typename T> int mlp_masks_t(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);
+// hmcx_mlp_pred.hip: the fused path's eligibility (shape, alignment, LDS) and the call itself
+bool mlp_pred_fused_ok(const hmcx_ctx*, const hmcx_mlp_predictive_args*);
+template <typename T> int mlp_predictive_t(hmcx_ctx*, const hmcx_mlp_predictive_args*);
 
 }  // namespace hmcx

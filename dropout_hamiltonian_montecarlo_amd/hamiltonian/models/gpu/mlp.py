@@ -16,18 +16,23 @@ on the device from Philox (hmcx_mlp_masks, keyed by the model's seed and a call 
 ``masks='off'`` disables dropout; an explicit ``masks=[m1, m2, m3]`` (each [B, n_mid]) injects
 them — the parity mode against oracle/models.py::mlp.
 """
+import collections
 import ctypes
 
 import numpy as np
 import torch
 
-from dropout_hamiltonian_montecarlo_amd._native import (HmcxError, MlpLeapfrogArgs, MlpParams, MLP_MASK_SLOT0,
-                                                        MLP_MASKS_FIXED, MLP_MASKS_NONE, MLP_MASKS_PHILOX, context,
-                                                        dtype_code, ptr)
+from dropout_hamiltonian_montecarlo_amd._native import (HmcxError, MlpLeapfrogArgs, MlpParams, MlpPredictiveArgs,
+                                                        MLP_MASK_SLOT0, MLP_MASKS_FIXED, MLP_MASKS_NONE,
+                                                        MLP_MASKS_PHILOX, context, dtype_code, ptr)
 
 from .softmax import _batch, as_device
 
 MLP_PARAM_NAMES = ('/l1/W', '/l1/b', '/l2/W', '/l2/b', '/l3/W', '/l3/b')
+
+# posterior_predictive's result (host NumPy arrays; the last three are None without labels)
+Predictive = collections.namedtuple('Predictive', ('mean', 'pred', 'entropy', 'expected_entropy', 'mutual_information',
+                                                   'lppd', 'draw_nll', 'draw_accuracy'))
 
 
 def mlp_param_shapes(n_in, n_mid, n_out):
@@ -265,3 +270,107 @@ class mlp:
             e = np.exp(z - z.max(axis=1, keepdims=True))
             return e / e.sum(axis=1, keepdims=True)
         return z.argmax(axis=1)
+
+    # -------------------------------------------------------------- posterior predictive (extension)
+    def _stacked(self, posterior):
+        """{name: [..., *shape]} → six contiguous device tensors [S, *shape] (leading dimensions flattened
+        row-major) and their MlpParams; names and shapes checked as _params does."""
+        ts, S = [], None
+        for k in MLP_PARAM_NAMES:
+            if k not in posterior:
+                raise HmcxError("mlp: missing parameter %r (expected %s)" % (k, MLP_PARAM_NAMES))
+            t = self._dev(posterior[k])
+            shp = self.shapes[k]
+            nl = t.dim() - len(shp)
+            if nl < 0 or tuple(t.shape[nl:]) != shp:
+                raise HmcxError("mlp: %s has shape %s, expected [..., %s]" % (k, tuple(t.shape), shp))
+            t = t.reshape((-1,) + shp).contiguous()
+            if S is None:
+                S = t.shape[0]
+            elif t.shape[0] != S:
+                raise HmcxError("mlp: %s holds %d parameter sets, the others %d" % (k, t.shape[0], S))
+            ts.append(t)
+        if S < 1:
+            raise HmcxError("mlp: the posterior holds no parameter set")
+        mp = MlpParams()
+        for i, t in enumerate(ts):
+            mp.p[i] = t.data_ptr()
+        return ts, mp, S
+
+    def posterior_predictive(self, posterior, X_test, y=None, masks=None, n_dropout=1, path=0):
+        """Model averaging on the device in one libhmcx call (hmcx_mlp_predictive): over the S parameter
+        sets of ``posterior`` ({name: [..., *shape]}, e.g. what ``sample`` returns, or [chains, epochs, …])
+        and ``n_dropout`` dropout draws per set, D = S·n_dropout draws in all (draw d = s·n_dropout + t).
+        Returns ``Predictive`` of host arrays: mean [N, n_out] class probabilities, pred [N] (their argmax),
+        entropy [N] of the mean, expected_entropy [N] (mean entropy of the draws), mutual_information [N]
+        = entropy − expected_entropy and, with labels ``y``, lppd [N] = log mean_d p_d[n, y_n],
+        draw_nll [D] (each draw's mean cross-entropy) and draw_accuracy [D]; those three are None without y.
+        masks: None draws Philox masks (the model's seed and call counter, as ``predict`` does: the next
+        draw_masks / predict continues after these D slots); 'off' disables dropout (n_dropout must be 1);
+        an array [D, 3, N, n_mid] injects them.  path: 0 by shape, 1 general, 2 fused (include/hmcx.h)."""
+        X = self._dev(X_test)
+        if X.dim() != 2 or X.shape[1] != self.n_in:
+            raise HmcxError("mlp: X_test must be [N, %d]" % self.n_in)
+        N, T = X.shape[0], int(n_dropout)
+        if T < 1:
+            raise ValueError("n_dropout must be >= 1")
+        ts, mp, S = self._stacked(posterior)
+        D = S * T
+        a = MlpPredictiveArgs()
+        a.dtype, a.N, a.n_in, a.n_mid, a.n_out, a.S, a.T = self.code, N, self.n_in, self.n_mid, self.n_out, S, T
+        a.path = int(path)
+        a.X, a.par = X.data_ptr(), mp
+        m = None
+        if masks is None:
+            a.mask_mode = MLP_MASKS_PHILOX
+            a.seed, a.chain, a.step = self.seed, 0, 0xFFFFFFFF
+            a.slot0 = (MLP_MASK_SLOT0 + self._mask_calls) & 0xFFFFFFFF
+            self._mask_calls += D
+        elif isinstance(masks, str):
+            if masks != 'off':
+                raise ValueError("masks must be None, 'off' or an array [D, 3, N, n_mid]")
+            if T != 1:
+                raise ValueError("masks='off' makes every draw of a parameter set the same: n_dropout must be 1")
+            a.mask_mode = MLP_MASKS_NONE
+        else:
+            m = self._dev(masks)
+            if tuple(m.shape) != (D, 3, N, self.n_mid):
+                raise HmcxError("mlp: masks must be [%d, 3, %d, %d]" % (D, N, self.n_mid))
+            a.mask_mode, a.masks = MLP_MASKS_FIXED, m.data_ptr()
+        yt = None
+        if y is not None:
+            yt = y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))
+            yt = yt.to(self.device, torch.int32).contiguous()
+            if yt.dim() != 1 or yt.shape[0] != N:
+                raise HmcxError("mlp: y must be integer labels [N]")
+            a.y = yt.data_ptr()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        mean, pred = torch.empty((N, self.n_out), **f64), torch.empty(N, **i32)
+        ent, eent = torch.empty(N, **f64), torch.empty(N, **f64)
+        a.out_mean, a.out_pred = mean.data_ptr(), pred.data_ptr()
+        a.out_entropy, a.out_exp_entropy = ent.data_ptr(), eent.data_ptr()
+        lppd = nll = corr = None
+        if yt is not None:
+            lppd, nll, corr = torch.empty(N, **f64), torch.empty(D, **f64), torch.empty(D, **i32)
+            a.out_lppd, a.out_draw_nll, a.out_draw_correct = lppd.data_ptr(), nll.data_ptr(), corr.data_ptr()
+        ctx = context(self.device)
+        ctx.check(ctx.lib.hmcx_mlp_predictive(ctx.h, ctypes.byref(a)), "hmcx_mlp_predictive")
+        host = [None if t is None else t.cpu().numpy() for t in (mean, pred, ent, eent, lppd, nll, corr)]
+        del ts, m, yt, X                                  # read by the launches the copies above waited for
+        mean, pred, ent, eent, lppd, nll, corr = host
+        return Predictive(mean, pred, ent, eent, ent - eent, lppd, nll,
+                          None if corr is None else corr / float(N))
+
+    def predict_posterior(self, posterior, X_test, prob=False, **kw):
+        """Posterior predictive over the parameter sets of ``posterior`` (softmax.predict_posterior's
+        contract): the mean class probabilities (prob=True) or their argmax.  Keywords go to
+        posterior_predictive (masks, n_dropout, path)."""
+        r = self.posterior_predictive(posterior, X_test, **kw)
+        return r.mean if prob else r.pred
+
+    def predict_stochastic(self, par, X_test, prob=False, n_dropout=10, **kw):
+        """MC dropout of one parameter set: the reference's predict (train mode, mlp.py:84-96) averaged
+        over n_dropout mask draws on the device."""
+        r = self.posterior_predictive(par, X_test, n_dropout=n_dropout, **kw)
+        return r.mean if prob else r.pred

@@ -473,6 +473,50 @@ typedef struct hmcx_mlp_leapfrog_args {
 } hmcx_mlp_leapfrog_args;
 int hmcx_mlp_hmc_leapfrog(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* a);
 
+/* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
+ * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
+ * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
+ * arithmetic of hmcx_mlp_loss, p_d = softmax(z_d) (max-subtracted).  Masks of draw d:
+ *   HMCX_MLP_MASKS_NONE    no dropout (T must be 1);
+ *   HMCX_MLP_MASKS_FIXED   block d of masks [D][3][N][n_mid] (dtype);
+ *   HMCX_MLP_MASKS_PHILOX  the values hmcx_mlp_masks(ctx, dtype, N, n_mid, seed, chain, step, slot0 + d)
+ *                          writes (slot0 + D must not wrap 2^32), drawn where they are used.
+ * path: 0 picks by shape, 1 the general path (one hmcx_mlp_loss forward per draw, then a reduce launch),
+ * 2 the fused row-block kernel (an error when the shape is not eligible: n_mid a multiple of 32 up to 256,
+ * n_out <= 16, n_in a multiple of 8, 16-byte aligned operands, and 16 rows of X, h1 and h2 within the
+ * 160 KiB of LDS).  path 0 takes the fused kernel where it is eligible and D >= 2 (there it measured
+ * faster at every point) and the general path elsewhere.
+ * Outputs (device; each may be NULL; float64 unless noted), sums over draws and rows in float64 and in
+ * a fixed order, so equal calls give equal bits:
+ *   out_mean [N][n_out]      (1/D) Σ_d p_d
+ *   out_pred int32 [N]       argmax_k of the mean, lowest index on ties
+ *   out_entropy [N]          −Σ_k m·log m of the mean (0·log 0 = 0)
+ *   out_exp_entropy [N]      (1/D) Σ_d H[p_d]
+ * and, with labels y (device int32 [N]; asking for one of these without y is an error):
+ *   out_lppd [N]             log((1/D) Σ_d p_d[n][y_n])
+ *   out_draw_nll [D]         the mean cross-entropy of draw d (what hmcx_mlp_loss returns for it)
+ *   out_draw_correct int32 [D]   #{n : argmax z_d[n] = y_n}
+ * Stream-ordered; returns once enqueued. */
+typedef struct hmcx_mlp_predictive_args {
+  int dtype;
+  int N, n_in, n_mid, n_out, S, T;
+  int mask_mode, path;
+  const void* X;           /* device [N][n_in] */
+  const int32_t* y;        /* device [N] or NULL */
+  hmcx_mlp_params par;     /* device, each [S][shape] */
+  const void* masks;       /* device [D][3][N][n_mid], FIXED */
+  uint64_t seed;
+  uint32_t chain, step, slot0;
+  double* out_mean;
+  int32_t* out_pred;
+  double* out_entropy;
+  double* out_exp_entropy;
+  double* out_lppd;
+  double* out_draw_nll;
+  int32_t* out_draw_correct;
+} hmcx_mlp_predictive_args;
+int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a);
+
 /* on = 0: hmcx_mlp_sghmc_run stops fusing layer 2 and layer 3 into one launch (no cross-workgroup
  * exchange; one more launch per forward) — the recovery path after out_abort; on = 1 restores it. */
 int hmcx_set_mlp_fuse(hmcx_ctx* ctx, int on);
