@@ -738,40 +738,14 @@ int hmcx_sumsq(hmcx_ctx* ctx, int dtype, const void* x, int64_t n, double* out) 
   return dtype == HMCX_F64 ? sumsq_t<double>(ctx, x, n, out) : sumsq_t<float>(ctx, x, n, out);
 }
 
-int hmcx_hmc_run(hmcx_ctx* ctx, const hmcx_hmc_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+// Validation and dispatch of both full-batch HMC entry points; `who` prefixes the messages.
+static int hmc_chains_checked(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a, const std::string& who) {
   if (a->model != HMCX_MODEL_SOFTMAX && a->model != HMCX_MODEL_LOGISTIC)
-    return set_error(ctx, HMCX_EINVAL, "hmc: model must be HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC");
-  if (a->model == HMCX_MODEL_LOGISTIC && a->K != 1) return set_error(ctx, HMCX_EINVAL, "hmc: logistic needs K = 1");
-  int rc = check_dims(ctx, a->dtype, a->B, a->D, a->K, 1);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "n_steps < 0");
-  if (a->n_steps == 0) return HMCX_OK;
-  if (!a->X || !a->Y || !a->W || !a->b || !a->eps || !a->n_iter || !a->u_accept || !a->out_A || !a->out_accepted ||
-      !a->out_nlp)
-    return set_error(ctx, HMCX_EINVAL, "null pointer");
-  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
-    return set_error(ctx, HMCX_EINVAL, "BUFFER noise needs noise and noise_off");
-  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "bad noise_mode");
-  for (int i = 0; i < a->n_steps; ++i)
-    if (a->n_iter[i] < 0) return set_error(ctx, HMCX_EINVAL, "n_iter < 0");
-  return a->dtype == HMCX_F64 ? hmc_run_t<double>(ctx, a) : hmc_run_t<float>(ctx, a);
-}
-
-int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  if (a->model != HMCX_MODEL_SOFTMAX && a->model != HMCX_MODEL_LOGISTIC)
-    return set_error(ctx, HMCX_EINVAL, "hmc_chains: model must be HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC");
-  if (a->model == HMCX_MODEL_LOGISTIC && a->K != 1)
-    return set_error(ctx, HMCX_EINVAL, "hmc_chains: logistic needs K = 1");
-  if (a->C < 1) return set_error(ctx, HMCX_EINVAL, "hmc_chains: C < 1");
-  if (a->K > 64) return set_error(ctx, HMCX_EUNSUPPORTED, "hmc_chains: K > 64");
+    return set_error(ctx, HMCX_EINVAL, who + ": model must be HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC");
+  if (a->model == HMCX_MODEL_LOGISTIC && a->K != 1) return set_error(ctx, HMCX_EINVAL, who + ": logistic needs K = 1");
   int rc = check_dims(ctx, a->dtype, a->B, a->D, a->K, a->C);
   if (rc) return rc;
-  if (a->C > 65535) return set_error(ctx, HMCX_EUNSUPPORTED, "hmc_chains: more than 65535 chains");
+  if (a->C > 65535) return set_error(ctx, HMCX_EUNSUPPORTED, who + ": more than 65535 chains");
   if ((long long)a->D * a->K + a->K > 0x7fffffffLL) return set_error(ctx, HMCX_EUNSUPPORTED, "too many parameters");
   if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "n_steps < 0");
   if (a->n_steps == 0) return HMCX_OK;
@@ -785,6 +759,31 @@ int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a) {
   for (size_t i = 0; i < (size_t)a->n_steps * a->C; ++i)
     if (a->n_iter[i] < 0) return set_error(ctx, HMCX_EINVAL, "n_iter < 0");
   return a->dtype == HMCX_F64 ? hmc_chains_run_t<double>(ctx, a) : hmc_chains_run_t<float>(ctx, a);
+}
+
+int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  return hmc_chains_checked(ctx, a, "hmc_chains");
+}
+
+// The one-chain call is the C = 1 case of the chain call.
+int hmcx_hmc_run(hmcx_ctx* ctx, const hmcx_hmc_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  hmcx_hmc_chains_args c{};
+  c.dtype = a->dtype; c.model = a->model;
+  c.B = a->B; c.D = a->D; c.K = a->K; c.C = 1; c.n_steps = a->n_steps;
+  c.alpha = a->alpha; c.log_prior = a->log_prior;
+  c.lp_const[0] = a->lp_const[0]; c.lp_const[1] = a->lp_const[1];
+  c.X = a->X; c.Y = a->Y;
+  c.eps = a->eps; c.n_iter = a->n_iter; c.u_accept = a->u_accept;
+  c.noise_mode = a->noise_mode; c.noise = a->noise; c.noise_off = a->noise_off;
+  c.seed = a->seed; c.chain0 = a->chain; c.step_base = a->step_base;
+  c.W = a->W; c.b = a->b;
+  c.out_A = a->out_A; c.out_accepted = a->out_accepted; c.out_nlp = a->out_nlp;
+  c.out_E = a->out_E; c.out_trace = a->out_trace; c.out_mom = a->out_mom;
+  return hmc_chains_checked(ctx, &c, "hmc");
 }
 
 int hmcx_mvn_eval(hmcx_ctx* ctx, int dim, int C, const double* mu, const double* prec, double nlp_const,

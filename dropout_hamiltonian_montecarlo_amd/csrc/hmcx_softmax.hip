@@ -31,10 +31,10 @@
 
 namespace hmcx {
 
-// Chain-batched full-batch HMC (hmc_chains_run_t): what follows gradient evaluation e of a chain whose
-// trajectory has n leapfrog iterations — the rule hmc_run_t applies on the host for its one chain.
-// 0 once the chain is past its last evaluation (e > 2n) or does not move (n = 0).
-__device__ __forceinline__ int hmc_chain_flags(int e, int n) {
+// Full-batch HMC (hmc_chains_run_t): what follows gradient evaluation e of a chain whose trajectory has
+// n leapfrog iterations.  0 once the chain is past its last evaluation (e > 2n) or does not move (n = 0).
+// Evaluated per chain in the HMCC kernels, on the host for a one-chain call.
+__host__ __device__ __forceinline__ int hmc_chain_flags(int e, int n) {
   if (n <= 0 || e > 2 * n) return 0;
   if (e == 0) return HMC_HALF_W;                               // hmc.py:47 then iteration 0, weights
   if (e & 1) return HMC_KICK_W | HMC_HALF_B;                   // after the weights' drift
@@ -968,80 +968,25 @@ int axpy_t(hmcx_ctx* ctx, int mode, int64_t n, double a, const void* x, void* y)
 }
 
 // ------------------------------------------------------------------ full-batch HMC, linear models
-// hmc.py:39-64 with the softmax / logistic model, one chain.  State: q = (W, b) (caller's buffers),
-// the proposal (Wn, bn) and its momentum (pW, pb) in the workspace.  Per step:
-//   k_hmc_init     p0 (hmc.py:41), proposal := q, Σp0² partials
-//   [n_iter ≥ 1]   1 + 2·n_iter gradient evaluations at the proposal: k_fwd(FWD_GRAD) + k_grad(GRAD_HMC)
-//                  whose epilogue applies the kicks/drifts that follow that evaluation (HmcFlags)
-//   k_fwd(FWD_LL)  log-likelihood of the proposal
-//   k_hmc_accept   energies (hmc.py:67-79), MH decision, nlp of the kept state (carried to the next
-//                  step as its E_current's nlp: the same kernel output, so no recomputation)
-//   k_hmc_commit   q := proposal if accepted; trace row of the kept state
+// hmc.py:39-64 with the softmax / logistic model, C chains in one call (C > 1: the intent of
+// hmc_multicore.py:22-38, one hmc.sample per worker; hmcx_hmc_run is the C = 1 case).  State q = (W, b)
+// (caller's buffers), the proposal (Wn, bn) and its momentum (pW, pb) in the workspace, all in the
+// [D][C·K] / [C·K] layout of the SGHMC chains, so k_fwd / k_grad run all chains as one GEMM (make_tiling
+// packs min(64/K, C) chains per tile).  Per step:
+//   k_hmcc_init    p0 (hmc.py:41), proposal := q, Σp0² partials                       grid (nDB, C)
+//   max_c(1 + 2·n_iter[c]) × [k_fwd(FWD_GRAD) + k_grad(GRAD_HMC)] at the proposals; the epilogue applies
+//                  the kicks/drifts that follow that evaluation (HmcFlags, hmc_chain_flags).  C > 1: each
+//                  chain takes them from (evaluation index, n_iter[c]) on the device, a chain past its last
+//                  evaluation writes nothing and tiles of finished chains exit before the GEMM (HMCC
+//                  instantiations).  C = 1: the host passes the flags and the plain instantiations run
+//   k_fwd(FWD_LL)  log-likelihood of the proposals (skipped when no chain moves)
+//   k_hmcc_accept  energies (hmc.py:67-79), MH decision, nlp of the kept state; HmcState per chain is
+//                  carried to the next step as its E_current's nlp (the same kernel output, so no
+//                  recomputation)                                                     grid (C)
+//   k_hmcc_commit  q := proposal where accepted; trace rows of the kept states        grid (⌈P/256⌉, C)
+// Element i = d·K + k of chain c lives at (i / K)·N + c·K + i % K, N = C·K.
 struct HmcState {
   double ll, sW, sb;   // log-likelihood and Σθ² (weights, bias) of the current state q
-};
-
-template <typename T>
-struct HmcInitArgs {
-  int D, K, P, nDB;
-  int noise_mode; const double* noise; int64_t noff;
-  uint64_t seed; uint32_t chain, step;
-  const T* W; const T* b; T* Wn; T* bn; T* pW; T* pb; T* mom;
-  double* kin0_part;   // [nDB + 1]: Σ pW0² per block, then Σ pb0²
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_hmc_init(HmcInitArgs<T> a) {
-  __shared__ double ksh[256];
-  const int tid = threadIdx.x, K = a.K;
-  const int e0 = blockIdx.x * 16 * K, ne = min(16 * K, a.D * K - e0);
-  double kin = 0.0;
-  for (int e = tid; e < ne; e += 256) {
-    const int i = e0 + e;
-    const T p = a.noise_mode == HMCX_NOISE_BUFFER ? (T)a.noise[a.noff + i]
-                                                  : philox_normal_t<T>(a.seed, a.chain, a.step, 0u, (uint32_t)i);
-    a.pW[i] = p;
-    a.Wn[i] = a.W[i];
-    if (a.mom) a.mom[i] = p;
-    kin += (double)p * (double)p;
-  }
-  ksh[tid] = kin;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) ksh[tid] += ksh[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) a.kin0_part[blockIdx.x] = ksh[0];
-  if (blockIdx.x == 0) {
-    __syncthreads();
-    double kb = 0.0;
-    if (tid < K) {
-      const int i = a.D * K + tid;
-      const T p = a.noise_mode == HMCX_NOISE_BUFFER ? (T)a.noise[a.noff + i]
-                                                    : philox_normal_t<T>(a.seed, a.chain, a.step, 0u, (uint32_t)i);
-      a.pb[tid] = p;
-      a.bn[tid] = a.b[tid];
-      if (a.mom) a.mom[i] = p;
-      kb = (double)p * (double)p;
-    }
-    ksh[tid] = kb;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (tid < s) ksh[tid] += ksh[tid + s];
-      __syncthreads();
-    }
-    if (tid == 0) a.kin0_part[a.nDB] = ksh[0];
-  }
-}
-
-template <typename T>
-struct HmcAcceptArgs {
-  int D, K, nRB, nDB, n_iter, first, logistic;
-  double u, neg_inv_n, log_prior, lpc0, lpc1, half_alpha;
-  const double* kin0_part; const double* ll0_part; const double* ll1_part;
-  const T* W; const T* b; const T* Wn; const T* bn; const T* pW; const T* pb;
-  HmcState* st;
-  double* out_A; int32_t* out_acc; double* out_nlp; double* out_E;
 };
 
 // Fixed-order Σ f(i) for i < n over the 256 threads of the block.
@@ -1061,176 +1006,6 @@ __device__ inline double block_sum256(int n, F f, double* sh) {
   return r;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_hmc_accept(HmcAcceptArgs<T> a) {
-  __shared__ double sh[256];
-  const int DK = a.D * a.K;
-  const bool moved = a.n_iter > 0;
-  // current state: computed at the call's first step, carried afterwards
-  double ll0, sW0, sb0;
-  if (a.first) {
-    ll0 = block_sum256(a.nRB, [&](int i) { return a.ll0_part[i]; }, sh);
-    sW0 = a.logistic ? block_sum256(DK, [&](int i) { const double v = (double)a.W[i]; return v * v; }, sh) : 0.0;
-    sb0 = a.logistic ? block_sum256(a.K, [&](int i) { const double v = (double)a.b[i]; return v * v; }, sh) : 0.0;
-  } else {
-    ll0 = a.st->ll; sW0 = a.st->sW; sb0 = a.st->sb;
-  }
-  const double S0W = block_sum256(a.nDB, [&](int i) { return a.kin0_part[i]; }, sh);
-  double ll1 = ll0, sW1 = sW0, sb1 = sb0, S1W = 0.0, S1b = 0.0;
-  if (moved) {
-    ll1 = block_sum256(a.nRB, [&](int i) { return a.ll1_part[i]; }, sh);
-    if (a.logistic) {
-      sW1 = block_sum256(DK, [&](int i) { const double v = (double)a.Wn[i]; return v * v; }, sh);
-      sb1 = block_sum256(a.K, [&](int i) { const double v = (double)a.bn[i]; return v * v; }, sh);
-    }
-    S1W = block_sum256(DK, [&](int i) { const double v = (double)a.pW[i]; return v * v; }, sh);
-    S1b = block_sum256(a.K, [&](int i) { const double v = (double)a.pb[i]; return v * v; }, sh);
-  }
-  if (threadIdx.x == 0) {
-    auto nlp = [&](double ll, double sW, double sb) {
-      double lp = a.log_prior;                                   // softmax.py:22-30 (constant)
-      if (a.logistic) lp = (((0.0 + a.lpc0) - a.half_alpha * sW) + a.lpc1) - a.half_alpha * sb;   // logistic.py:15-21
-      return a.neg_inv_n * (ll + lp);
-    };
-    const double K0 = (0.0 + 0.5 * S0W) + 0.5 * a.kin0_part[a.nDB];
-    const double nlp0 = nlp(ll0, sW0, sb0);
-    const double Ecur = nlp0 + K0;
-    double Enew = Ecur, A = 1.0;
-    if (moved) {
-      const double K1 = (0.0 + 0.5 * S1W) + 0.5 * S1b;           // ½Σ(−p)² = ½Σp² (hmc.py:55-56)
-      Enew = nlp(ll1, sW1, sb1) + K1;
-      const double x = exp(Ecur - Enew);
-      A = (x < 1.0) ? x : 1.0;                                   // Python min(1, x): NaN → 1
-    }
-    const int acc = a.u < A;
-    a.out_A[0] = A;
-    a.out_acc[0] = acc;
-    if (a.out_E) { a.out_E[0] = Ecur; a.out_E[1] = Enew; }
-    HmcState s;
-    if (acc && moved) { s.ll = ll1; s.sW = sW1; s.sb = sb1; }
-    else { s.ll = ll0; s.sW = sW0; s.sb = sb0; }
-    *a.st = s;
-    a.out_nlp[0] = (acc && moved) ? nlp(ll1, sW1, sb1) : nlp0;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_hmc_commit(int DK, int K, const int32_t* acc, const T* Wn, const T* bn,
-                                                    T* W, T* b, T* trace) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool take = *acc != 0;
-  if (i < DK) {
-    T v = W[i];
-    if (take) { v = Wn[i]; W[i] = v; }
-    if (trace) trace[i] = v;
-  } else if (i < DK + K) {
-    T v = b[i - DK];
-    if (take) { v = bn[i - DK]; b[i - DK] = v; }
-    if (trace) trace[i] = v;
-  }
-}
-
-template <typename T>
-int hmc_run_t(hmcx_ctx* ctx, const hmcx_hmc_args* s) {
-  const int B = s->B, D = s->D, K = s->K, DK = D * K, P = DK + K;
-  const bool logistic = s->model == HMCX_MODEL_LOGISTIC;
-  const int link = logistic ? LINK_SIGMOID : LINK_SOFTMAX;
-  const Tiling t = make_tiling(B, D, K, 1);
-  Workspace ws(ctx);
-  T *Wn, *bn, *pW, *pb, *diff, *csp;
-  double *kin0, *ll0p, *ll1p;
-  HmcState* st;
-  do {
-    ws.reset();
-    Wn = ws.take<T>(DK); bn = ws.take<T>(K); pW = ws.take<T>(DK); pb = ws.take<T>(K);
-    diff = ws.take<T>((size_t)B * K); csp = ws.take<T>((size_t)t.nRB * K);
-    kin0 = ws.take<double>(t.nDB + 1); ll0p = ws.take<double>(t.nRB); ll1p = ws.take<double>(t.nRB);
-    st = ws.take<HmcState>(1);
-  } while (ws.retry());
-  if (ws.failed) return HMCX_ENOMEM;
-  begin_call(ctx);
-  int rc;
-  if ((rc = timing_begin(ctx, ctx->stream))) return rc;
-  GraphScope gs(ctx);
-  hipStream_t st_ = ctx->stream;
-  T* W = (T*)s->W;
-  T* b = (T*)s->b;
-  // log-likelihood of the call's starting state (its nlp enters step 0's E_current)
-  {
-    FwdArgs<T> f = fwd_args<T>(s->X, s->Y, W, b, B, D, K, 1, t, FWD_LL);
-    f.link = link;
-    f.ll_part = ll0p;
-    HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
-  }
-  for (int i = 0; i < s->n_steps; ++i) {
-    const double eps = s->eps[i];
-    const int n = s->n_iter[i];
-    HmcInitArgs<T> ia{};
-    ia.D = D; ia.K = K; ia.P = P; ia.nDB = t.nDB;
-    ia.noise_mode = s->noise_mode; ia.noise = s->noise;
-    ia.noff = s->noise_mode == HMCX_NOISE_BUFFER ? s->noise_off[i] : 0;
-    ia.seed = s->seed; ia.chain = s->chain; ia.step = s->step_base + (uint32_t)i;
-    ia.W = W; ia.b = b; ia.Wn = Wn; ia.bn = bn; ia.pW = pW; ia.pb = pb;
-    ia.mom = s->out_mom ? (T*)s->out_mom + (size_t)i * P : nullptr;
-    ia.kin0_part = kin0;
-    hipLaunchKernelGGL(k_hmc_init<T>, dim3(t.nDB), dim3(256), 0, st_, ia);
-    HMCX_HIP(ctx, hipGetLastError());
-    const int n_eval = n > 0 ? 1 + 2 * n : 0;
-    for (int e = 0; e < n_eval; ++e) {
-      FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, 1, t, FWD_GRAD);
-      f.link = link;
-      f.diff = diff; f.colsum_part = csp;
-      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
-      GradArgs<T> g = grad_args<T>((const T*)s->X, diff, csp, B, D, K, 1, t, GRAD_HMC, s->alpha);
-      g.eps = (T)eps; g.half_eps = (T)(0.5 * eps);
-      g.W = Wn; g.b = bn; g.pW = pW; g.pb = pb;
-      int fl;
-      if (e == 0) fl = HMC_HALF_W;                               // hmc.py:47 then it 0, weights
-      else if (e & 1) fl = HMC_KICK_W | HMC_HALF_B;              // after the weights' drift
-      else fl = HMC_KICK_B | (e < 2 * n ? HMC_HALF_W : 0);       // after the bias' drift
-      g.hmc_flags = fl;
-      HMCX_HIP(ctx, launch_grad<T>(g, t, st_));
-    }
-    if (n > 0) {
-      FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, 1, t, FWD_LL);
-      f.link = link;
-      f.ll_part = ll1p;
-      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
-    }
-    HmcAcceptArgs<T> aa{};
-    aa.D = D; aa.K = K; aa.nRB = t.nRB; aa.nDB = t.nDB; aa.n_iter = n; aa.first = i == 0; aa.logistic = logistic;
-    aa.u = s->u_accept[i]; aa.neg_inv_n = -1.0 / (double)B; aa.log_prior = s->log_prior;
-    aa.lpc0 = s->lp_const[0]; aa.lpc1 = s->lp_const[1]; aa.half_alpha = 0.5 * s->alpha;
-    aa.kin0_part = kin0; aa.ll0_part = ll0p; aa.ll1_part = ll1p;
-    aa.W = W; aa.b = b; aa.Wn = Wn; aa.bn = bn; aa.pW = pW; aa.pb = pb;
-    aa.st = st;
-    aa.out_A = s->out_A + i; aa.out_acc = s->out_accepted + i; aa.out_nlp = s->out_nlp + i;
-    aa.out_E = s->out_E ? s->out_E + 2 * i : nullptr;
-    hipLaunchKernelGGL(k_hmc_accept<T>, dim3(1), dim3(256), 0, st_, aa);
-    HMCX_HIP(ctx, hipGetLastError());
-    T* tr = s->out_trace ? (T*)s->out_trace + (size_t)i * P : nullptr;
-    if (n > 0 || tr) {
-      hipLaunchKernelGGL(k_hmc_commit<T>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st_, DK, K,
-                         s->out_accepted + i, Wn, bn, W, b, tr);
-      HMCX_HIP(ctx, hipGetLastError());
-    }
-  }
-  if ((rc = gs.finish())) return rc;
-  return timing_end(ctx, ctx->stream);
-}
-
-// ------------------------------------------------------------------ full-batch HMC, C chains
-// hmc_multicore.py:22-38's intent (one hmc.sample per worker) as C chains of one call.  State, proposal
-// and momentum in the [D][C·K] / [C·K] layout of the SGHMC chains, so k_fwd / k_grad run all chains as
-// one GEMM (make_tiling packs min(64/K, C) chains per tile).  Per step:
-//   k_hmcc_init    p0, proposal := q, Σp0² partials                                  grid (nDB, C)
-//   max_c(1 + 2·n_iter[c]) × [k_fwd(FWD_GRAD) + k_grad(GRAD_HMC)] over all chains: each chain takes its
-//                  kicks/drifts from (evaluation index, n_iter[c]) — hmc_chain_flags — and a chain past
-//                  its last evaluation writes nothing; tiles of finished chains exit before the GEMM
-//   k_fwd(FWD_LL)  log-likelihood of the proposals
-//   k_hmcc_accept  energies, MH decision, carried HmcState per chain                 grid (C)
-//   k_hmcc_commit  q := proposal where accepted; trace rows                          grid (⌈P/256⌉, C)
-// Element i = d·K + k of chain c lives at (i / K)·N + c·K + i % K.
 template <typename T>
 struct HmcCInitArgs {
   int D, K, C, N, P, nDB;
@@ -1297,7 +1072,7 @@ struct HmcCAcceptArgs {
   double* out_A; int32_t* out_acc; double* out_nlp; double* out_E;   // [C] rows of this step
 };
 
-// k_hmc_accept for chain blockIdx.x: the same sums in the same order, over the chain's columns.
+// Chain blockIdx.x: every sum over the chain's columns in a fixed order (block_sum256).
 template <typename T>
 __global__ __launch_bounds__(256) void k_hmcc_accept(HmcCAcceptArgs<T> a) {
   __shared__ double sh[256];
@@ -1382,10 +1157,13 @@ int hmc_chains_run_t(hmcx_ctx* ctx, const hmcx_hmc_chains_args* s) {
   const size_t nsc = (size_t)s->n_steps * C;
   Workspace ws(ctx);
   T *Wn, *bn, *pW, *pb, *diff, *csp;
-  double *kin0, *ll0p, *ll1p, *d_u;
-  int32_t* d_niter;
-  int64_t* d_noff;
+  double *kin0, *ll0p, *ll1p;
   HmcState* st;
+  // the per-(step, chain) schedule goes to the device in one copy
+  const bool buffer = s->noise_mode == HMCX_NOISE_BUFFER;
+  const void* hsrc[3] = {s->n_iter, s->u_accept, buffer ? s->noise_off : nullptr};
+  const size_t hbytes[3] = {nsc * sizeof(int32_t), nsc * sizeof(double), buffer ? nsc * sizeof(int64_t) : 0};
+  char *sched, *dp[3];
   do {
     ws.reset();
     Wn = ws.take<T>((size_t)D * N); bn = ws.take<T>(N); pW = ws.take<T>((size_t)D * N); pb = ws.take<T>(N);
@@ -1393,15 +1171,15 @@ int hmc_chains_run_t(hmcx_ctx* ctx, const hmcx_hmc_chains_args* s) {
     kin0 = ws.take<double>((size_t)(t.nDB + 1) * C);
     ll0p = ws.take<double>((size_t)t.nRB * C); ll1p = ws.take<double>((size_t)t.nRB * C);
     st = ws.take<HmcState>(C);
-    d_niter = ws.take<int32_t>(nsc); d_u = ws.take<double>(nsc); d_noff = ws.take<int64_t>(nsc);
+    sched = ws.take<char>(packed_bytes(3, hbytes));
   } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
   begin_call(ctx);
-  int rc = upload(ctx, d_niter, s->n_iter, nsc * sizeof(int32_t));
+  int rc = upload_packed(ctx, sched, 3, hsrc, hbytes, dp);
   if (rc) return rc;
-  if ((rc = upload(ctx, d_u, s->u_accept, nsc * sizeof(double)))) return rc;
-  if (s->noise_mode == HMCX_NOISE_BUFFER && (rc = upload(ctx, d_noff, s->noise_off, nsc * sizeof(int64_t))))
-    return rc;
+  const int32_t* d_niter = reinterpret_cast<const int32_t*>(dp[0]);
+  const double* d_u = reinterpret_cast<const double*>(dp[1]);
+  const int64_t* d_noff = reinterpret_cast<const int64_t*>(dp[2]);   // read in BUFFER mode only
   if ((rc = timing_begin(ctx, ctx->stream))) return rc;
   GraphScope gs(ctx);
   hipStream_t st_ = ctx->stream;
@@ -1433,12 +1211,18 @@ int hmc_chains_run_t(hmcx_ctx* ctx, const hmcx_hmc_chains_args* s) {
       FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, C, t, FWD_GRAD);
       f.link = link;
       f.diff = diff; f.colsum_part = csp;
-      f.iter = e; f.n_iter = niter;
-      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
       GradArgs<T> g = grad_args<T>((const T*)s->X, diff, csp, B, D, K, C, t, GRAD_HMC, s->alpha);
       g.eps = (T)eps; g.half_eps = (T)(0.5 * eps);
       g.W = Wn; g.b = bn; g.pW = pW; g.pb = pb;
-      g.iter = e; g.n_iter = niter;
+      if (C == 1) {
+        // one chain: n_iter stays null, which selects the plain k_fwd / k_grad instantiations (the
+        // chain-aware epilogue costs a one-chain call 0.4 %)
+        g.hmc_flags = hmc_chain_flags(e, nmax);
+      } else {
+        f.iter = e; f.n_iter = niter;
+        g.iter = e; g.n_iter = niter;
+      }
+      HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
       HMCX_HIP(ctx, launch_grad<T>(g, t, st_));
     }
     if (nmax > 0) {
@@ -1982,8 +1766,6 @@ template int softmax_predict_t<double>(hmcx_ctx*, const void*, int, int, int, in
                                        int);
 template int sgd_run_t<float>(hmcx_ctx*, const hmcx_sgd_args*);
 template int sgd_run_t<double>(hmcx_ctx*, const hmcx_sgd_args*);
-template int hmc_run_t<float>(hmcx_ctx*, const hmcx_hmc_args*);
-template int hmc_run_t<double>(hmcx_ctx*, const hmcx_hmc_args*);
 template int hmc_chains_run_t<float>(hmcx_ctx*, const hmcx_hmc_chains_args*);
 template int hmc_chains_run_t<double>(hmcx_ctx*, const hmcx_hmc_chains_args*);
 template int axpy_t<float>(hmcx_ctx*, int, int64_t, double, const void*, void*);

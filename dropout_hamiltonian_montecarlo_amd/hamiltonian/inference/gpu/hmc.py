@@ -10,10 +10,12 @@ Device paths:
 
 * MVN model (config 1): every step of a burn-in / sampling phase runs in ONE device launch
   (hmcx_hmc_mvn_run, one thread per chain);
-* softmax (CPU prior) and logistic models: a burn-in / sampling phase is ONE hmcx_hmc_run call —
-  momentum, every kick/drift (fused into the gradient kernels' epilogues), the energies, the MH
-  accept and the commit run on the device; the host only draws the schedule (path lengths, accept
+* softmax (CPU prior) and logistic models: a burn-in / sampling phase is ONE hmcx_hmc_chains_run
+  call — momentum, every kick/drift (fused into the gradient kernels' epilogues), the energies, the
+  MH accept and the commit run on the device; the host only draws the schedule (path lengths, accept
   uniforms and, in noise='numpy' mode, the momenta) in the reference's order;
+  Both are written for C chains (_schedule .. _chains_fused): sample runs them with C = 1,
+  hmc_multicore.sample_multicore with C = ncores;
 * the MLP: a step's whole leapfrog trajectory is ONE hmcx_mlp_hmc_leapfrog call (device gradients,
   kicks and drifts enqueued from C in the reference's order); the energies go out as device pieces
   read back once.  A model that overrides grad (or HMCX_HMC_HOST_LOOP=1) runs the reference's loop
@@ -37,6 +39,8 @@ def _host_loop():
 
 
 class hmc:
+    NOISE_CHUNK = 1 << 24          # float64 momentum normals handed to one hmcx_hmc_chains_run call
+
     def __init__(self, model, start_p, path_length=1.0, step_size=0.1, verbose=True,
                  noise='numpy', seed=0, chain=0):
         self.start = start_p
@@ -55,69 +59,22 @@ class hmc:
     def draw_momentum(self, rng):                                           # hmc.py:82-87
         return {var: rng.normal(0, 1, size=np.shape(self.start[var])) for var in self.start.keys()}
 
-    # ------------------------------------------------------------------ MVN fused path
-    def _mvn_run(self, x, n_steps, rng):
-        m = self.model
-        dim = m.dim
-        eps = np.full(n_steps, self.step_size, dtype=np.float64)
-        n_iter = np.empty(n_steps, dtype=np.int32)
-        u = np.empty(n_steps, dtype=np.float64)
-        noise = np.empty((n_steps, dim), dtype=np.float64)
-        for s in range(n_steps):
-            g = (self.global_step + s) & 0xFFFFFFFF
-            if self.noise == 'numpy':
-                noise[s] = rng.normal(0, 1, size=dim)                          # hmc.py:41 (draw_momentum)
-                L = np.ceil(2 * np.random.rand() * self.path_length / self.step_size)  # :46
-                u[s] = np.random.rand()                                        # :61
-            else:
-                noise[s] = nat.philox_normals(self.seed, self.chain, g, 0, 0, dim, dtype="f64")
-                L = np.ceil(2 * nat.philox_uniforms(self.seed, self.chain, g, nat.SLOT_PATH, 1)[0]
-                            * self.path_length / self.step_size)
-                u[s] = nat.philox_uniforms(self.seed, self.chain, g, nat.SLOT_ACCEPT, 1)[0]
-            n_iter[s] = _n_iter(L)
-        dev = m.device
-        noise_d = torch.from_numpy(noise.ravel()).to(dev)
-        noff = np.arange(n_steps, dtype=np.int64) * dim
-        out_A = torch.empty(n_steps, dtype=torch.float64, device=dev)
-        out_acc = torch.empty(n_steps, dtype=torch.int32, device=dev)
-        out_nlp = torch.empty(n_steps, dtype=torch.float64, device=dev)
-        out_tr = torch.empty(n_steps * dim, dtype=torch.float64, device=dev)
-        a = nat.MvnArgs()
-        a.dim, a.C, a.n_steps = dim, 1, n_steps
-        a.mu, a.prec, a.nlp_const = ptr(m.mu), ptr(m.prec), m.nlp_const
-        a.eps = eps.ctypes.data_as(nat.c_dblp)
-        a.n_iter = n_iter.ctypes.data_as(nat.c_i32p)
-        a.u_accept = u.ctypes.data_as(nat.c_dblp)
-        # both modes hand the device the host-drawn momenta (philox: the f64 Philox stream's host twin),
-        # so the returned momentums are exactly the ones used (dim = 2: nothing to save on the device)
-        a.noise_mode = nat.NOISE_BUFFER
-        a.noise = ptr(noise_d)
-        a.noise_off = noff.ctypes.data_as(nat.c_i64p)
-        a.seed, a.chain0, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
-        a.x = ptr(x)
-        a.out_A, a.out_accepted, a.out_nlp, a.out_trace = ptr(out_A), ptr(out_acc), ptr(out_nlp), ptr(out_tr)
-        ctx = nat.context(dev)
-        ctx.check(ctx.lib.hmcx_hmc_mvn_run(ctx.h, a), "hmcx_hmc_mvn_run")
-        self.global_step += n_steps
-        A = out_A.cpu().numpy()
-        acc = out_acc.cpu().numpy().astype(bool)
-        if self.trace is not None:
-            self.trace.extend({'L': float(n + 1), 'A': float(A[s]), 'accepted': bool(acc[s]),
-                               'eps': self.step_size} for s, n in enumerate(n_iter))
-        return A, acc, out_nlp.cpu().numpy(), out_tr.cpu().numpy().reshape(n_steps, dim), noise
-
     def sample(self, niter=1e4, burnin=1e3, rng=None, **args):              # hmc.py:90-119
         if rng is None:
             rng = np.random.RandomState()
         niter, nburn = int(niter), int(burnin)
         if self.noise == 'numpy':
             self.draw_momentum(rng)                                          # hmc.py:93 consumes RNG
-        step_size_tuning = DualAveragingStepSize(self.step_size)
-        if self.model._hmcx_model == 'mvn_gaussian':
-            return self._sample_fused(niter, nburn, burnin, rng, step_size_tuning)
-        if self._linear_fused():
-            return self._sample_linear(niter, nburn, burnin, rng, step_size_tuning, args)
-        return self._sample_generic(niter, nburn, burnin, rng, step_size_tuning, args)
+        mvn = self.model._hmcx_model == 'mvn_gaussian'
+        if not mvn and not self._linear_fused():
+            return self._sample_generic(niter, nburn, burnin, rng, DualAveragingStepSize(self.step_size), args)
+        # one chain of the chain-batched code; burn-in losses are printed every burnin / 10 steps of the
+        # caller's raw burnin (hmc.py:97)
+        results, traces, _ = self._chains_fused(niter, nburn, 1, [rng], None if mvn else args, burnin / 10)
+        if self.trace is not None:
+            # this entry point records n_iter + 1, which differs from the drawn L only for L = 0
+            self.trace.extend(dict(t, L=max(t['L'], 1.0)) for t in traces[0])
+        return results[0]
 
     # ------------------------------------------------------------------ softmax / logistic fused path
     def _linear_fused(self):
@@ -131,7 +88,7 @@ class hmc:
         return X.contiguous(), y.contiguous()
 
     def _linear_model_args(self, a, Xd, Yd, D, K, n_steps):
-        """The model part of hmcx_hmc_args / hmcx_hmc_chains_args (same field names in both)."""
+        """The model part of hmcx_hmc_chains_args."""
         m = self.model
         a.dtype, a.model = m.code, nat.MODEL_LOGISTIC if m._hmcx_model == 'logistic' else nat.MODEL_SOFTMAX
         a.B, a.D, a.K, a.n_steps = Xd.shape[0], D, K, n_steps
@@ -144,117 +101,211 @@ class hmc:
             a.log_prior = m.log_prior_const([np.shape(self.start[v]) for v in self.start])
         a.X, a.Y = ptr(Xd), ptr(Yd)
 
-    def _linear_run(self, W, b, data, n_steps, rng, record):
-        """n_steps HMC steps in one hmcx_hmc_run call.  Host work: the schedule in the reference's
-        draw order (hmc.py:41 momentum from rng, :46 path length and :61 accept uniform from the
-        global np.random) or, with noise='philox', path lengths / uniforms from the Philox twin."""
+    # ------------------------------------------------------------------ fused routes: C chains per call
+    # hmc.sample is one chain of this code (C = 1, rngs = [rng]); hmc_multicore.sample_multicore runs C.
+    def _schedule(self, n_steps, C, P, rngs, step0, host_mom):
+        """Steps step0.. of a phase: path iterations, accept uniforms and path lengths L, [n_steps, C]
+        each, and the host momenta [n_steps, C, P] (None where the device draws them).
+        noise='numpy': per step in the reference's draw order — hmc.py:41 the momentum of chains
+        0..C−1, each from its rng (variables in start order), then :46 the path length and :61 the accept
+        uniform from the global np.random, shared by the chains.  An rng that is the global stream itself
+        therefore sees the reference's interleaving.  noise='philox': hmcx_philox_schedule, and with
+        host_mom the host twin of the device's float64 momentum stream (the MVN route)."""
+        if self.noise == 'numpy':
+            n1 = np.empty(n_steps, dtype=np.int32)
+            u1 = np.empty(n_steps, dtype=np.float64)
+            L1 = np.empty(n_steps, dtype=np.float64)
+            noise = np.empty((n_steps, C, P), dtype=np.float64)
+            for s in range(n_steps):
+                for c in range(C):
+                    mom = self.draw_momentum(rngs[c])                                       # hmc.py:41
+                    noise[s, c] = np.concatenate([np.reshape(mom[v], -1) for v in self.start])
+                L1[s] = np.ceil(2 * np.random.rand() * self.path_length / self.step_size)   # hmc.py:46
+                n1[s] = _n_iter(L1[s])
+                u1[s] = np.random.rand()                                                    # hmc.py:61
+            rep = lambda v: np.ascontiguousarray(np.repeat(v[:, None], C, axis=1))
+            return rep(n1), rep(u1), rep(L1), noise
+        g0 = self.global_step + step0
+        eps = np.full(n_steps, self.step_size, dtype=np.float64)
+        L, n_iter, u = nat.philox_schedule(self.seed, self.chain, C, g0, self.path_length, eps)
+        noise = None
+        if host_mom:
+            noise = np.empty((n_steps, C, P), dtype=np.float64)
+            for s in range(n_steps):
+                for c in range(C):
+                    noise[s, c] = nat.philox_normals(self.seed, self.chain + c, (g0 + s) & 0xFFFFFFFF, 0, 0, P,
+                                                     dtype="f64")
+        return n_iter, u, L, noise
+
+    def _hmc_chains_call(self, W, b, data, n_iter, u, noise=None, step_base=0, trace=None, mom=None):
+        """One hmcx_hmc_chains_run call.  W [D, C·K], b [C·K] device tensors (updated in place); n_iter,
+        u host [n_steps, C]; noise a device float64 tensor [n_steps, C, P] (BUFFER) or None (PHILOX);
+        trace / mom device [n_steps, C, P] tensors in the model dtype or None.  Returns host arrays
+        A, accepted, nlp [n_steps, C] and E [n_steps, C, 2]."""
         m = self.model
         Xd, Yd = data
-        D, K = W.shape
+        n_iter = np.ascontiguousarray(n_iter, dtype=np.int32)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        n_steps, C = n_iter.shape
+        D = W.shape[0]
+        K = W.shape[1] // C
         P = D * K + K
-        eps = np.full(n_steps, self.step_size, dtype=np.float64)
-        n_iter = np.empty(n_steps, dtype=np.int32)
-        u = np.empty(n_steps, dtype=np.float64)
-        noise = np.empty((n_steps, P), dtype=np.float64) if self.noise == 'numpy' else None
-        for s in range(n_steps):
-            g = (self.global_step + s) & 0xFFFFFFFF
-            if self.noise == 'numpy':
-                mom = self.draw_momentum(rng)                                  # hmc.py:41
-                noise[s, :D * K] = mom['weights'].reshape(-1)
-                noise[s, D * K:] = mom['bias'].reshape(-1)
-                L = np.ceil(2 * np.random.rand() * self.path_length / self.step_size)   # hmc.py:46
-                n_iter[s] = _n_iter(L)
-                u[s] = np.random.rand()                                        # hmc.py:61
-            else:
-                L = np.ceil(2 * nat.philox_uniforms(self.seed, self.chain, g, nat.SLOT_PATH, 1)[0]
-                            * self.path_length / self.step_size)
-                n_iter[s] = _n_iter(L)
-                u[s] = nat.philox_uniforms(self.seed, self.chain, g, nat.SLOT_ACCEPT, 1)[0]
         dev = m.device
-        noise_d = torch.from_numpy(noise.ravel()).to(dev) if noise is not None else None
-        noff = np.arange(n_steps, dtype=np.int64) * P
-        out_f = torch.empty(4 * n_steps, dtype=torch.float64, device=dev)        # A, nlp, E (2)
-        out_acc = torch.empty(n_steps, dtype=torch.int32, device=dev)
-        tr = torch.empty((n_steps, P), dtype=m.dtype, device=dev) if record else None
-        mo = torch.empty((n_steps, P), dtype=m.dtype, device=dev) if (record and noise is None) else None
-        a = nat.HmcArgs()
+        eps = np.full(n_steps, self.step_size, dtype=np.float64)
+        noff = np.arange(n_steps * C, dtype=np.int64) * P
+        out_f = torch.empty(4 * n_steps * C, dtype=torch.float64, device=dev)     # A, nlp, E (2)
+        out_acc = torch.empty(n_steps * C, dtype=torch.int32, device=dev)
+        nsc = n_steps * C
+        a = nat.HmcChainsArgs()
         self._linear_model_args(a, Xd, Yd, D, K, n_steps)
+        a.C = C
         a.eps = eps.ctypes.data_as(nat.c_dblp)
         a.n_iter = n_iter.ctypes.data_as(nat.c_i32p)
         a.u_accept = u.ctypes.data_as(nat.c_dblp)
         a.noise_mode = nat.NOISE_BUFFER if noise is not None else nat.NOISE_PHILOX
+        a.noise = ptr(noise)
+        a.noise_off = noff.ctypes.data_as(nat.c_i64p)
+        a.seed, a.chain0, a.step_base = self.seed, self.chain & 0xFFFFFFFF, step_base & 0xFFFFFFFF
+        a.W, a.b = ptr(W), ptr(b)
+        a.out_A, a.out_nlp, a.out_E = ptr(out_f[:nsc]), ptr(out_f[nsc:2 * nsc]), ptr(out_f[2 * nsc:])
+        a.out_accepted = ptr(out_acc)
+        a.out_trace, a.out_mom = ptr(trace), ptr(mom)
+        ctx = nat.context(dev)
+        ctx.check(ctx.lib.hmcx_hmc_chains_run(ctx.h, a), "hmcx_hmc_chains_run")
+        f = out_f.cpu().numpy()
+        return (f[:nsc].reshape(n_steps, C), out_acc.cpu().numpy().astype(bool).reshape(n_steps, C),
+                f[nsc:2 * nsc].reshape(n_steps, C), f[2 * nsc:].reshape(n_steps, C, 2))
+
+    def _linear_phase(self, st, n_steps, C, rngs, record):
+        """One burn-in / sampling phase of the linear models: A, acc, nlp, L [n_steps, C] and, when
+        recording, the host trace and momenta [n_steps, C, P] and the device trace.  BUFFER-mode momenta
+        (noise='numpy') of one call are capped at NOISE_CHUNK values; a longer phase is several calls
+        over consecutive steps, which changes no result (the carried state of a call is recomputed by
+        the same kernel on the same values)."""
+        W, b, data, P = st
+        dev, dt = self.model.device, self.model.dtype
+        tr = torch.empty((n_steps, C, P), dtype=dt, device=dev) if record else None
+        host_mom = self.noise == 'numpy'
+        mo = torch.empty((n_steps, C, P), dtype=dt, device=dev) if (record and not host_mom) else None
+        chunk = max(1, self.NOISE_CHUNK // (C * P)) if host_mom else n_steps
+        outs, Ls, moms = [], [], []
+        for s0 in range(0, n_steps, chunk):
+            s1 = min(n_steps, s0 + chunk)
+            n_iter, u, L, noise = self._schedule(s1 - s0, C, P, rngs, s0, False)
+            Ls.append(L)
+            if record and host_mom:
+                moms.append(noise)
+            outs.append(self._hmc_chains_call(W, b, data, n_iter, u,
+                                              torch.from_numpy(noise.reshape(-1)).to(dev) if host_mom else None,
+                                              self.global_step + s0, tr[s0:s1] if record else None,
+                                              mo[s0:s1] if mo is not None else None))
+        self.global_step += n_steps
+        A, acc, nlp = (np.concatenate([o[i] for o in outs], axis=0) for i in range(3))
+        trace = mom = None
+        if record:
+            trace = tr.cpu().numpy().astype(np.float64)
+            mom = np.concatenate(moms, axis=0) if host_mom else mo.cpu().numpy().astype(np.float64)
+        return A, acc, nlp, np.concatenate(Ls, axis=0), trace, mom, tr
+
+    def _mvn_phase(self, st, n_steps, C, rngs, record):
+        """The same for the MVN model: hmcx_hmc_mvn_run with C chains, x [C, dim]."""
+        x, dim = st
+        m = self.model
+        # both modes hand the device the host-drawn momenta (philox: the f64 Philox stream's host twin),
+        # so the returned momentums are exactly the ones used (dim = 2: nothing to save on the device)
+        n_iter, u, L, noise = self._schedule(n_steps, C, dim, rngs, 0, True)
+        dev = m.device
+        nsc = n_steps * C
+        eps = np.full(n_steps, self.step_size, dtype=np.float64)
+        noise_d = torch.from_numpy(noise.reshape(-1)).to(dev)
+        noff = np.arange(nsc, dtype=np.int64) * dim
+        out_A = torch.empty(nsc, dtype=torch.float64, device=dev)
+        out_acc = torch.empty(nsc, dtype=torch.int32, device=dev)
+        out_nlp = torch.empty(nsc, dtype=torch.float64, device=dev)
+        out_tr = torch.empty((n_steps, C, dim), dtype=torch.float64, device=dev)
+        a = nat.MvnArgs()
+        a.dim, a.C, a.n_steps = dim, C, n_steps
+        a.mu, a.prec, a.nlp_const = ptr(m.mu), ptr(m.prec), m.nlp_const
+        a.eps = eps.ctypes.data_as(nat.c_dblp)
+        a.n_iter = n_iter.ctypes.data_as(nat.c_i32p)
+        a.u_accept = u.ctypes.data_as(nat.c_dblp)
+        a.noise_mode = nat.NOISE_BUFFER
         a.noise = ptr(noise_d)
         a.noise_off = noff.ctypes.data_as(nat.c_i64p)
-        a.seed, a.chain, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
-        a.W, a.b = ptr(W), ptr(b)
-        a.out_A, a.out_nlp, a.out_E = ptr(out_f[:n_steps]), ptr(out_f[n_steps:2 * n_steps]), ptr(out_f[2 * n_steps:])
-        a.out_accepted = ptr(out_acc)
-        a.out_trace, a.out_mom = ptr(tr), ptr(mo)
+        a.seed, a.chain0, a.step_base = self.seed, self.chain & 0xFFFFFFFF, self.global_step & 0xFFFFFFFF
+        a.x = ptr(x)
+        a.out_A, a.out_accepted, a.out_nlp, a.out_trace = ptr(out_A), ptr(out_acc), ptr(out_nlp), ptr(out_tr)
         ctx = nat.context(dev)
-        ctx.check(ctx.lib.hmcx_hmc_run(ctx.h, a), "hmcx_hmc_run")
+        ctx.check(ctx.lib.hmcx_hmc_mvn_run(ctx.h, a), "hmcx_hmc_mvn_run")
         self.global_step += n_steps
-        f = out_f.cpu().numpy()
-        A, nlp = f[:n_steps], f[n_steps:2 * n_steps]
-        acc = out_acc.cpu().numpy().astype(bool)
-        if self.trace is not None:
-            self.trace.extend({'L': float(n + 1), 'A': float(A[s]), 'accepted': bool(acc[s]), 'eps': self.step_size}
-                              for s, n in enumerate(n_iter))
-        trace = tr.cpu().numpy().astype(np.float64) if tr is not None else None
-        mom = (noise if noise is not None else mo.cpu().numpy().astype(np.float64)) if record else None
-        return A, acc, nlp, trace, mom
+        A = out_A.cpu().numpy().reshape(n_steps, C)
+        acc = out_acc.cpu().numpy().astype(bool).reshape(n_steps, C)
+        nlp = out_nlp.cpu().numpy().reshape(n_steps, C)
+        return A, acc, nlp, L, out_tr.cpu().numpy() if record else None, noise, out_tr
 
     def _split(self, flat):
         D, K = np.shape(self.start['weights'])
         return {'weights': flat[:D * K].reshape(D, K).copy(), 'bias': flat[D * K:].reshape(np.shape(self.start['bias'])).copy()}
 
-    def _sample_linear(self, niter, nburn, burnin, rng, tuning, args):
+    def _chains_fused(self, niter, nburn, C, rngs, args, burn_print):
+        """C chains in one device call per phase; per chain, in chain order, what hmc.sample prints and
+        returns.  args None: the MVN model.  burn_print: a burn-in loss is printed every burn_print
+        steps.  Returns the chains' (posterior, loss, positions, momentums), their per-step trace
+        records (L as drawn) and the sampling phase's device trace [niter, C, P] (None if niter = 0)."""
         m = self.model
-        data = self._linear_data(args)
-        W = m._dev(self.start['weights']).clone()
-        b = m._dev(np.reshape(self.start['bias'], -1)).clone()
-        p_accept = None
-        if nburn > 0:
-            A, _, nlp, _, _ = self._linear_run(W, b, data, nburn, rng, False)
-            for i in range(nburn):
-                if self.verbose is not None and (i % (burnin / 10) == 0):
-                    print('loss: {0:.4f}'.format(nlp[i]), file=self.out)
-            p_accept = A[-1]
-        _, avg_step_size = tuning.update(p_accept)
-        print('adapted step size : ', avg_step_size, file=self.out)
-        before = np.concatenate([W.cpu().numpy().reshape(-1), b.cpu().numpy().reshape(-1)]).astype(np.float64)
-        if niter == 0:
-            return {v: np.zeros((0,) + np.shape(self.start[v])) for v in self.start}, np.zeros(0), [], []
-        A, acc, nlp, tr, mom = self._linear_run(W, b, data, niter, rng, True)
-        positions = [[self._split(before if i == 0 else tr[i - 1])] for i in range(niter)]
-        momentums = [[self._split(mom[i])] for i in range(niter)]
-        for i in range(niter):
-            if self.verbose and (i % (niter / 10) == 0):
-                print('loss: {0:.4f}'.format(nlp[i]), file=self.out)
-        D, K = np.shape(self.start['weights'])
-        posterior = {'weights': tr[:, :D * K].reshape((niter,) + np.shape(self.start['weights'])),
-                     'bias': tr[:, D * K:].reshape((niter,) + np.shape(self.start['bias']))}
-        self.last_state = {'weights': W, 'bias': b}
-        return posterior, nlp, positions, momentums
-
-    def _sample_fused(self, niter, nburn, burnin, rng, tuning):
-        x = torch.as_tensor(np.asarray(self.start['x'], dtype=np.float64)).to(self.model.device).contiguous().clone()
-        p_accept = None
-        if nburn > 0:
-            A, acc, nlp, tr, _ = self._mvn_run(x, nburn, rng)
-            for i in range(nburn):
-                if self.verbose is not None and (i % (burnin / 10) == 0):
-                    print('loss: {0:.4f}'.format(nlp[i]), file=self.out)
-            p_accept = A[-1]
-        _, avg_step_size = tuning.update(p_accept)
-        print('adapted step size : ', avg_step_size, file=self.out)
-        x_before = x.cpu().numpy().copy()
-        A, acc, nlp, tr, mom = self._mvn_run(x, niter, rng)
-        positions = [[{'x': (x_before if i == 0 else tr[i - 1]).copy()}] for i in range(niter)]
-        momentums = [[{'x': mom[i].copy()}] for i in range(niter)]
-        for i in range(niter):
-            if self.verbose and (i % (niter / 10) == 0):
-                print('loss: {0:.4f}'.format(nlp[i]), file=self.out)
-        return {'x': tr}, nlp, positions, momentums
+        mvn = args is None
+        if mvn:
+            x0 = np.asarray(self.start['x'], dtype=np.float64).reshape(-1)
+            x = torch.as_tensor(np.tile(x0, (C, 1))).to(m.device).contiguous()
+            st, phase = (x, x0.size), self._mvn_phase
+            state = lambda: x.cpu().numpy().copy()                           # [C, dim]
+            split = lambda flat: {'x': flat.reshape(np.shape(self.start['x'])).copy()}
+        else:
+            data = self._linear_data(args)
+            D, K = np.shape(self.start['weights'])
+            W = m._dev(self.start['weights']).clone().repeat(1, C).contiguous()          # [D][C·K]
+            b = m._dev(np.reshape(self.start['bias'], -1)).clone().repeat(C).contiguous()
+            st, phase = (W, b, data, D * K + K), self._linear_phase
+            state = lambda: np.concatenate([W.cpu().numpy().reshape(D, C, K).transpose(1, 0, 2).reshape(C, D * K),
+                                            b.cpu().numpy().reshape(C, K)], axis=1).astype(np.float64)
+            split = self._split
+        burn = phase(st, nburn, C, rngs, False) if nburn > 0 else None
+        before = state()
+        samp = phase(st, niter, C, rngs, True) if niter > 0 else None
+        if not mvn:
+            self.last_state = {'weights': st[0], 'bias': st[1]}
+        traces = [[] for _ in range(C)]
+        results = []
+        for c in range(C):
+            p_accept = None
+            if burn is not None:
+                A, acc, nlp, L = burn[:4]
+                for i in range(nburn):
+                    if self.verbose is not None and (i % burn_print == 0):
+                        print('loss: {0:.4f}'.format(nlp[i, c]), file=self.out)
+                p_accept = A[-1, c]
+                traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
+                                  'eps': self.step_size} for i in range(nburn))
+            _, avg_step_size = DualAveragingStepSize(self.step_size).update(p_accept)
+            print('adapted step size : ', avg_step_size, file=self.out)
+            if samp is None:
+                results.append(({v: np.zeros((0,) + np.shape(self.start[v])) for v in self.start}, np.zeros(0), [], []))
+                continue
+            A, acc, nlp, L, tr, mom = samp[:6]
+            traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
+                              'eps': self.step_size} for i in range(niter))
+            positions = [[split(before[c] if i == 0 else tr[i - 1, c])] for i in range(niter)]
+            momentums = [[split(mom[i, c])] for i in range(niter)]
+            for i in range(niter):
+                if self.verbose and (i % (niter / 10) == 0):
+                    print('loss: {0:.4f}'.format(nlp[i, c]), file=self.out)
+            if mvn:
+                posterior = {'x': tr[:, c].copy()}
+            else:
+                posterior = {'weights': tr[:, c, :D * K].reshape((niter,) + np.shape(self.start['weights'])),
+                             'bias': tr[:, c, D * K:].reshape((niter,) + np.shape(self.start['bias']))}
+            results.append((posterior, nlp[:, c].copy(), positions, momentums))
+        return results, traces, samp[6] if samp is not None else None
 
     # ------------------------------------------------------------------ generic path (device grads)
     def _K(self, p):                                                         # hmc.py:74-79

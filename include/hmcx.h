@@ -299,7 +299,9 @@ int hmcx_mvn_eval(hmcx_ctx* ctx, int dim, int C, const double* mu, const double*
  * log_prior: softmax — the constant `log_prior` (softmax.py:22-30); logistic — Σ_var
  * (lp_const[var] − ½·alpha·Σθ_var²) with Σθ² on the device (logistic.py:15-21).
  * X [N][D] (full batch: B = N rows), Y [N][K] one-hot (softmax) or [N] 0/1 (logistic, K = 1).
- * Noise as hmcx_sampler_args (BUFFER: noise_off[s], P = D·K + K momentum normals per step). */
+ * Noise as hmcx_sampler_args (BUFFER: noise_off[s], P = D·K + K momentum normals per step).
+ * hmcx_hmc_run is the C = 1 case of hmcx_hmc_chains_run below (chain0 = chain): one implementation,
+ * the same validation, bit-identical results. */
 typedef struct hmcx_hmc_args {
   int dtype;
   int model;               /* HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC                  */
@@ -337,7 +339,7 @@ int hmcx_hmc_run(hmcx_ctx* ctx, const hmcx_hmc_args* a);
  * n_iter): a chain past its last evaluation (or with n_iter = 0: q kept, A = 1) writes nothing.
  * BUFFER noise: P = D·K + K momentum normals per (step, chain) at noise_off[s*C + c] (weights
  * row-major, then bias).  PHILOX: chain c draws Philox(seed, chain0 + c, step_base + s, slot 0, elem),
- * the stream of a one-chain hmcx_hmc_run with chain = chain0 + c. */
+ * the stream of a one-chain hmcx_hmc_run with chain = chain0 + c.  C = 1 is what hmcx_hmc_run runs. */
 typedef struct hmcx_hmc_chains_args {
   int dtype;
   int model;               /* HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC                  */

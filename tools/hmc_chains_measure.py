@@ -3,7 +3,8 @@ MNIST-shaped f64, N=60000, D=784, K=10, eps=1e-3, 10 steps, n_iter = 5 for all c
 Uses hmcx_set_timing / hmcx_get_timing: a warm-up, then the median of three calls.  HMCX_LIB names the
 library under dropout_hamiltonian_montecarlo_amd/lib/ to load (default libhmcx.so); with a build of an older
 commit that lacks hmcx_hmc_chains_run only the sequential hmcx_hmc_run figures are printed — the baseline
-of DESIGN §5.7.  One JSON line per figure (profiles/hmc_chains_measure.jsonl)."""
+of DESIGN §5.7.  Last, at the launch-bound N = 200: host wall ms of one hmcx_hmc_run call plus synchronize,
+median and quartiles of 21 calls.  --one-chain stops after the hmcx_hmc_run, C = 1 line.  One JSON line per figure (profiles/hmc_chains_measure.jsonl)."""
 import json
 import os
 import sys
@@ -17,23 +18,29 @@ from dropout_hamiltonian_montecarlo_amd import _native as nat  # noqa: E402
 from dropout_hamiltonian_montecarlo_amd._native import ptr  # noqa: E402
 
 N, D, K, S, NIT, EPS = 60000, 784, 10, 10, 5, 1e-3
+N_SMALL = 200
 P = D * K + K
 dev = torch.device("cuda:0")
 lib_name = os.environ.get("HMCX_LIB", "libhmcx.so")
 ctx = nat.context(dev)
 has_chains = hasattr(ctx.lib, "hmcx_hmc_chains_run")
 rs = np.random.RandomState(0)
-X = torch.as_tensor(rs.rand(N, D)).to(dev)
-lab = rs.randint(0, K, N)
-Yh = np.zeros((N, K))
-Yh[np.arange(N), lab] = 1.0
-Y = torch.as_tensor(Yh).to(dev)
+
+
+def problem(n):
+    X = torch.as_tensor(rs.rand(n, D)).to(dev)
+    Yh = np.zeros((n, K))
+    Yh[np.arange(n), rs.randint(0, K, n)] = 1.0
+    return X, torch.as_tensor(Yh).to(dev)
+
+
+X, Y = problem(N)
 log_prior = -1.234
 
 
 def common(a, C):
     a.dtype, a.model = nat.HMCX_F64, nat.MODEL_SOFTMAX
-    a.B, a.D, a.K, a.n_steps = N, D, K, S
+    a.B, a.D, a.K, a.n_steps = X.shape[0], D, K, S
     a.alpha, a.log_prior = 0.01, log_prior
     a.X, a.Y = ptr(X), ptr(Y)
     a.noise_mode = nat.NOISE_PHILOX
@@ -89,7 +96,7 @@ def timed(fn):
 
 
 def emit(**kw):
-    kw.update(lib=lib_name, N=N, D=D, K=K, steps=S, n_iter=NIT, dtype="f64")
+    kw.update(lib=lib_name, N=X.shape[0], D=D, K=K, steps=S, n_iter=NIT, dtype="f64")
     print(json.dumps(kw), flush=True)
 
 
@@ -106,6 +113,8 @@ timed(lambda: seq(1))
 one = sorted(timed(lambda: seq(1))[0] for _ in range(3))
 emit(what="hmcx_hmc_run", C=1, ms=one[1], all_ms=one)
 W1 = seq(1)[0][0].cpu().numpy()
+if "--one-chain" in sys.argv:      # only the C = 1 line: for A/B runs that alternate two libraries
+    sys.exit(0)
 for C in (6, 48):
     reps = 3 if one[1] * C * 3 < 90e3 else 1
     t = sorted(timed(lambda: seq(C))[0] for _ in range(reps))
@@ -120,3 +129,18 @@ if has_chains:
         # chain 0 of the batched call against the single-chain call on the same stream
         emit(what="chain0 max rel diff vs hmcx_hmc_run", C=C,
              value=float(np.max(np.abs(Wc[:, :K] - W1) / (np.abs(W1) + 1e-300))))
+
+# launch-bound shape: host wall time of one hmcx_hmc_run call plus synchronize (where per-call uploads
+# and launch overhead show), median of 21 calls after a warm-up
+X, Y = problem(N_SMALL)
+
+
+def wall():
+    t0 = time.perf_counter()
+    seq(1)
+    return (time.perf_counter() - t0) * 1e3
+
+
+wall()
+w = sorted(wall() for _ in range(21))
+emit(what="hmcx_hmc_run wall", C=1, ms=w[10], q1_ms=w[5], q3_ms=w[15], all_ms=w)
