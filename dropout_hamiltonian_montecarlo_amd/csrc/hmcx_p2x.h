@@ -76,52 +76,70 @@ __device__ inline bool p2_spin_over(unsigned long long t0, int* abort_flag, int 
   return false;
 }
 
+// ---- poll passes.  A pass issues its whole batch of loads unconditionally, folds every granule's two
+// epoch words into ONE miss word per thread (OR of (y ^ ep) | (w ^ ep): VALU only, no per-granule mask)
+// and tests it once: on zero the values are decoded straight from this pass's registers, otherwise the
+// next pass re-reads everything.  Nothing is carried from one pass to the next, which is safe because a
+// granule that carries epoch ep stays in place until its slot's next use of the same parity, and its
+// producer cannot reach that use before this consumer has published something it publishes only after
+// this consume (the argument is spelled out per region where hmcx_persist2.hip declares the regions).
+// Entries a thread does not want (absent producers, pskip, pairs past the end, want() false) are
+// aliased ONCE, before the loop, to the thread's first wanted granule: they match when it does and cost
+// no masking per pass.  A thread that wants nothing issues no load and does not spin.
+__device__ inline unsigned gran_miss(gran_t v, unsigned ep) { return (v.y ^ ep) | (v.w ^ ep); }
+// The one test of a pass.  The miss word goes through an opaque register: left transparent, the
+// compiler turns the OR of XORs back into one compare per epoch word, chained through a scalar mask.
+__device__ inline bool pass_complete(unsigned miss) {
+  asm volatile("" : "+v"(miss));
+  return miss == 0u;
+}
+// The tail of a pass that missed: bounded spin (clock read on the first miss, timeout and abort word
+// checked every 64th pass), then back off.  true: give up.
+__device__ inline bool p2_pass_missed(int spins, unsigned long long& t0, int* abort_flag, int where, unsigned ep) {
+  if (spins == 0) t0 = __builtin_amdgcn_s_memrealtime();
+  if ((spins & 63) == 63 && p2_spin_over(t0, abort_flag, where, ep)) return true;
+  if (HMCX_P2_SLEEP) __builtin_amdgcn_s_sleep(1);
+  return false;
+}
+
 // Polls one granule per producer p < np (p != pskip) at base0 + p·pstride + off until both epoch
-// words match.  Loads go out unpredicated in one batch of 8·NB (absent producers clamped to a
-// valid address and ignored); a pass re-reads the batch while any granule is missing.
+// words of every one match, in batches of 8·NB loads.
 // SUM: *sum = v_0 + v_1 + … in producer order; else v_p → dst[p·dstride].  false on timeout/abort.
 template <int NB, bool SUM, typename V, int AUX = 16>
 __device__ inline bool poll_nb(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int pskip, int off,
                                bool valid, unsigned ep, double* sum, int* abort_flag, V* dst, int dstride) {
   constexpr int N = 8 * NB;
-  unsigned pend = 0;
+  if (!valid) return true;
+  const int first = pskip == 0 ? 1 : 0;            // the first wanted producer
+  if (first >= np) {                               // a team of one that skips itself, or no producer
+    if (SUM) *sum = 0.0;
+    return true;
+  }
+  const int ofirst = (base0 + first * pstride + off) * 16;
   int o[N];
 #pragma unroll
-  for (int u = 0; u < N; ++u) {
-    const bool want = valid && u < np && u != pskip;
-    pend |= want ? 1u << u : 0u;
-    o[u] = (base0 + (want ? u * pstride + off : 0)) * 16;
-  }
-  double val[N];
-#pragma unroll
-  for (int u = 0; u < N; ++u) val[u] = 0.0;
+  for (int u = 0; u < N; ++u) o[u] = (u < np && u != pskip) ? (base0 + u * pstride + off) * 16 : ofirst;
+  gran_t v[N];
   unsigned long long t0 = 0;
-  for (int spins = 0; pend; ++spins) {
-    gran_t v[N];
+  for (int spins = 0;; ++spins) {
 #pragma unroll
     for (int u = 0; u < N; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[u], 0, AUX /* 16: sc1 */);
+    unsigned miss = 0;
 #pragma unroll
-    for (int u = 0; u < N; ++u)
-      if (((pend >> u) & 1u) && v[u].y == ep && v[u].w == ep) {
-        val[u] = decode(v[u]);
-        pend &= ~(1u << u);
-      }
-    if (!pend) break;
-    if (spins == 0) t0 = __builtin_amdgcn_s_memrealtime();
-    if ((spins & 63) == 63 && p2_spin_over(t0, abort_flag, base0, ep)) return false;
-    if (HMCX_P2_SLEEP) __builtin_amdgcn_s_sleep(1);
+    for (int u = 0; u < N; ++u) miss |= gran_miss(v[u], ep);
+    if (pass_complete(miss)) break;
+    if (p2_pass_missed(spins, t0, abort_flag, base0, ep)) return false;
   }
-  if (!valid) return true;
   if (SUM) {
-    double acc = val[0];
+    double acc = pskip == 0 ? 0.0 : decode(v[0]);
 #pragma unroll
     for (int u = 1; u < N; ++u)
-      if (u < np && u != pskip) acc += val[u];
+      if (u < np && u != pskip) acc += decode(v[u]);
     *sum = acc;
   } else {
 #pragma unroll
     for (int u = 0; u < N; ++u)
-      if (u < np && u != pskip) dst[u * dstride] = (V)val[u];
+      if (u < np && u != pskip) dst[u * dstride] = (V)decode(v[u]);
   }
   return true;
 }
@@ -136,54 +154,50 @@ __device__ inline bool poll(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, i
 }
 
 // NI items per thread (item j at granule offset off[j] of every producer block, valid bit j of vmask),
-// each summed over producers p < np in producer order: NI·8·NB loads per pass in one batch.
-// false on timeout/abort.
+// each summed over producers p < np in producer order: NI·8·NB loads per pass in one batch; sum[j] = 0
+// for an item that is not valid.  false on timeout/abort.
 // `work()` runs once while the first batch of loads is in flight (independent work hidden behind the
 // round's latency).
 template <int NI, int NB, typename Work>
 __device__ inline bool polln_nb(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, const int* off,
                                 unsigned vmask, unsigned ep, double* sum, int* abort_flag, Work work) {
   constexpr int N = 8 * NB, M = NI * N;
-  static_assert(M <= 64, "pending mask");
-  unsigned long long pend = 0;
+  vmask &= (1u << NI) - 1u;
+  if (!vmask || np <= 0) {
+    work();
+#pragma unroll
+    for (int j = 0; j < NI; ++j) sum[j] = 0.0;
+    return true;
+  }
+  int ofirst = 0;                                  // producer 0 of the first valid item
+#pragma unroll
+  for (int j = NI - 1; j >= 0; --j)
+    if ((vmask >> j) & 1u) ofirst = (base0 + off[j]) * 16;
   int o[M];
 #pragma unroll
   for (int u = 0; u < M; ++u) {
     const int j = u / N, p = u - j * N;
-    const bool want = ((vmask >> j) & 1u) && p < np;
-    pend |= want ? 1ull << u : 0ull;
-    o[u] = (base0 + (want ? p * pstride + off[j] : 0)) * 16;
+    o[u] = (((vmask >> j) & 1u) && p < np) ? (base0 + p * pstride + off[j]) * 16 : ofirst;
   }
-  double val[M];
-#pragma unroll
-  for (int u = 0; u < M; ++u) val[u] = 0.0;
+  gran_t v[M];
   unsigned long long t0 = 0;
-  bool worked = false;
-  for (int spins = 0; pend; ++spins) {
-    gran_t v[M];
+  for (int spins = 0;; ++spins) {
 #pragma unroll
     for (int u = 0; u < M; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[u], 0, 16 /* sc1 */);
     if (spins == 0) work();
-    worked = true;
+    unsigned miss = 0;
 #pragma unroll
-    for (int u = 0; u < M; ++u)
-      if (((pend >> u) & 1ull) && v[u].y == ep && v[u].w == ep) {
-        val[u] = decode(v[u]);
-        pend &= ~(1ull << u);
-      }
-    if (!pend) break;
-    if (spins == 0) t0 = __builtin_amdgcn_s_memrealtime();
-    if ((spins & 63) == 63 && p2_spin_over(t0, abort_flag, base0, ep)) return false;
-    if (HMCX_P2_SLEEP) __builtin_amdgcn_s_sleep(1);
+    for (int u = 0; u < M; ++u) miss |= gran_miss(v[u], ep);
+    if (pass_complete(miss)) break;
+    if (p2_pass_missed(spins, t0, abort_flag, base0, ep)) return false;
   }
-  if (!worked) work();
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
-    double acc = val[j * N];
+    double acc = decode(v[j * N]);
 #pragma unroll
     for (int p = 1; p < N; ++p)
-      if (p < np) acc += val[j * N + p];
-    sum[j] = acc;
+      if (p < np) acc += decode(v[j * N + p]);
+    sum[j] = ((vmask >> j) & 1u) ? acc : 0.0;
   }
   return true;
 }
@@ -200,73 +214,57 @@ __device__ inline bool polln(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, 
 // after the barrier, so sums are bit-identical to poll<true>.  Item i of producer p is granule
 // base0 + p·pstride + ioff(i); pairs with want(p, i) false are skipped.
 constexpr int QSTAGE = 4 * QTH;             // staged pairs per round (LDS doubles)
-template <int U, typename Off, typename Want>
-__device__ inline bool gather_u(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
-                                Want want, unsigned ep, int* abort_flag, double* stage) {
-  unsigned pend = 0;
-  int o[U], qi[U];
+// The body of every spread gather, U granules per thread: store(q, v) for each wanted pair
+// q = p·nitems + i (gather_u stages them, gather_st_u lets the caller choose the destination, e.g.
+// straight into the consumer's LDS layout, saving a staging copy and its barrier).
+template <int U, typename Off, typename Want, typename Store>
+__device__ inline bool gather_wst_u(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
+                                    Want want, unsigned ep, int* abort_flag, Store store) {
+  unsigned wm = 0;                                 // wanted pairs of this thread
+  int o[U];
   const int t0i = opaque((int)threadIdx.x);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int q = t0i + u * QTH;
     const int p = q / nitems, i = q - p * nitems;
     const bool w = q < np * nitems && want(p, i);
-    pend |= w ? 1u << u : 0u;
-    o[u] = (base0 + (w ? p * pstride + ioff(i) : 0)) * 16;
-    qi[u] = q;
+    wm |= w ? 1u << u : 0u;
+    o[u] = w ? (base0 + p * pstride + ioff(i)) * 16 : 0;
   }
+  if (!wm) return true;
+  int ofirst = 0;
+#pragma unroll
+  for (int u = U - 1; u >= 0; --u)
+    if ((wm >> u) & 1u) ofirst = o[u];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (!((wm >> u) & 1u)) o[u] = ofirst;
+  gran_t v[U];
   unsigned long long t0 = 0;
-  for (int spins = 0; pend; ++spins) {
-    gran_t v[U];
+  for (int spins = 0;; ++spins) {
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[u], 0, 16 /* sc1 */);
+    unsigned miss = 0;
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (((pend >> u) & 1u) && v[u].y == ep && v[u].w == ep) {
-        stage[qi[u]] = decode(v[u]);
-        pend &= ~(1u << u);
-      }
-    if (!pend) break;
-    if (spins == 0) t0 = __builtin_amdgcn_s_memrealtime();
-    if ((spins & 63) == 63 && p2_spin_over(t0, abort_flag, base0, ep)) return false;
-    if (HMCX_P2_SLEEP) __builtin_amdgcn_s_sleep(1);
+    for (int u = 0; u < U; ++u) miss |= gran_miss(v[u], ep);
+    if (pass_complete(miss)) break;
+    if (p2_pass_missed(spins, t0, abort_flag, base0, ep)) return false;
   }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if ((wm >> u) & 1u) store(t0i + u * QTH, decode(v[u]));
   return true;
 }
-// gather_u with the destination chosen per pair: store(q, v) for pair q = p·nitems + i (e.g. straight
-// into the consumer's LDS layout, saving a staging copy and its barrier).
+template <int U, typename Off, typename Want>
+__device__ inline bool gather_u(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
+                                Want want, unsigned ep, int* abort_flag, double* stage) {
+  return gather_wst_u<U>(rs, base0, pstride, np, nitems, ioff, want, ep, abort_flag,
+                         [&](int q, double v) { stage[q] = v; });
+}
 template <int U, typename Off, typename Store>
 __device__ inline bool gather_st_u(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
                                    unsigned ep, int* abort_flag, Store store) {
-  unsigned pend = 0;
-  int o[U], qi[U];
-  const int t0i = opaque((int)threadIdx.x);
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int q = t0i + u * QTH;
-    const int p = q / nitems, i = q - p * nitems;
-    const bool w = q < np * nitems;
-    pend |= w ? 1u << u : 0u;
-    o[u] = (base0 + (w ? p * pstride + ioff(i) : 0)) * 16;
-    qi[u] = q;
-  }
-  unsigned long long t0 = 0;
-  for (int spins = 0; pend; ++spins) {
-    gran_t v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, o[u], 0, 16 /* sc1 */);
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (((pend >> u) & 1u) && v[u].y == ep && v[u].w == ep) {
-        store(qi[u], decode(v[u]));
-        pend &= ~(1u << u);
-      }
-    if (!pend) break;
-    if (spins == 0) t0 = __builtin_amdgcn_s_memrealtime();
-    if ((spins & 63) == 63 && p2_spin_over(t0, abort_flag, base0, ep)) return false;
-    if (HMCX_P2_SLEEP) __builtin_amdgcn_s_sleep(1);
-  }
-  return true;
+  return gather_wst_u<U>(rs, base0, pstride, np, nitems, ioff, [](int, int) { return true; }, ep, abort_flag, store);
 }
 template <typename Off, typename Store>
 __device__ inline bool gather_st(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,

@@ -25,7 +25,8 @@
 //  * Transport: every value travels as one 16-byte granule {lo32, epoch, hi32, epoch} written by
 //    ONE `buffer_store_dwordx4 … sc1` and read by `buffer_load_dwordx4 … sc1`; a consumer re-reads
 //    a granule until both epoch words match (cdna_hip_programming.md §6 G16, recipe R2: the data
-//    is the flag).  Epochs count rounds within the call; the arena is zeroed before each launch.
+//    is the flag).  Epochs count rounds over the arena's whole life (each launch reserves a fresh
+//    range, sghmc_p2_t), so an epoch is never written twice and the arena is NOT cleared per launch.
 //    Measured on MI355X (tools/microbench_handoff.hip): one team round of 8 x 80-130 granules
 //    ≈ 1.4-1.6 µs, against 3-3.4 µs for payload + counter barrier.
 // All reductions run in a fixed order, so the replicated state is bit-identical in every
@@ -50,8 +51,28 @@ struct Q2Args {
   int noise_mode; const double* noise; const int64_t* noff;
   uint64_t seed; uint32_t chain0, step_base;
   void* W; void* b;
-  char* arena;                              // granule arena (zeroed per call)
-  int oXA, oXD, oXB, oXW, oXS;              // region offsets in granules
+  char* arena;                              // granule arena (the context's; epochs are unique over its life)
+  // Region offsets in granules.  XA, XD, XB, XW and XS are double-buffered by the parity of a per-region
+  // use counter, so a producer P overwrites the granule of its use u at its use u + 2.  The poll passes
+  // (hmcx_p2x.h) carry nothing from one pass to the next, so a consumer C needs every granule of use u to
+  // stay in place until C's pass that sees them all.  Every consume ends in a workgroup barrier (all_ok),
+  // so "P consumed" below means all of P's threads did.  Per region, for teams of any size:
+  //  XA (A-RS, row team): between P's uses u and u + 2 lies an A-AG consume of P (rounds run A, [A,] D, B,
+  //     [W,] A …) or an accept round (across a step boundary), in which P polls the header or the partials
+  //     of EVERY row-team member (a member that owns no softmax rows polls nothing in A-RS, but always
+  //     those).  C publishes them only after its consume of A(u).
+  //  XD (A-AG, row team): P reaches use u + 2 through its consume of D(u + 1), which polls C's block of
+  //     D(u + 1); C published it after its consume of D(u).
+  //  XB (B-RS / B all-reduce, feature team): the same through B(u + 1): with `bar` every member polls every
+  //     producer's whole block; without it the header threads poll all Gr headers.
+  //  XW (B-AG, `bar` off, feature team): a member may poll only the producers that own features, so W(u + 1)
+  //     does not order P behind C; but between W(u) and W(u + 2) P consumes a B-RS round, whose header it
+  //     polls from every member, and C publishes that B round only after its consume of W(u).
+  //  XS (accept, all G): P's consume of S(u + 1) polls C's partials, published after C's consume of S(u).
+  //  XC (commit, one use per launch): written once per launch with the launch's last epoch; the next
+  //     write is by the next launch on the same stream, which starts after every workgroup of this one,
+  //     workgroup 0 and its gather included, has ended.
+  int oXA, oXD, oXB, oXW, oXS;
   int oXC;                                  // commit round: one granule per workgroup
   int arena_bytes;
   int pad;                                  // line-aligned producer blocks (HMCX_P2_PAD, default on)
