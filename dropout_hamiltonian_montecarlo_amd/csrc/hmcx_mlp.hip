@@ -185,8 +185,6 @@ template <typename T> struct MMArgs {
   // workgroups of one row block meet in a tagged-granule arena (see k_mm)
   char* gx; int gx_bytes; unsigned ep; int* abort_flag;
   int N3; const T* bias3; T* gz;     // n_out, b3 and the gz output of the fused layer 3
-  T* h1out;                          // MM_L23: store the slice's columns of h1 = max((xw + b1)·m0, 0)
-  const T* H1;                       // MM_GA1: the gate from a stored h1 (no mask reads)
   int force_abort;                   // test knob (HMCX_MLP_FORCE_ABORT): raise the abort word, skip the publish
   unsigned long long* prof;          // HMCX_MLP_PROF: per-workgroup s_memrealtime stamps of the MM_L23 phases
   int xmap, xbx, xby;                // GEMM plane placement over the XCDs (xcd_place): 0 dispatch order, 1 y-major
@@ -205,7 +203,6 @@ template <typename T> struct MMProb {
   MaskSrc<T> ms;
   T* ga2; T* pb2; T* pb3; T* pw3; T* gz; double* lpart; T* colpart;
   char* gx;                          // MM_L23: the problem's own region of the granule arena
-  const T* H1;                       // MM_GA1: the gate from this problem's stored h1 (null: from xw, b1, m0)
 };
 template <typename T, int NP> struct MMProbsN {
   MMProb<T> p[NP];
@@ -541,7 +538,6 @@ __device__ __forceinline__ void mm_body(const MMArgs<T>& a, const PR& pr, const 
   const T* const oB = pp ? pp->B : a.B;
   T* const oC = pp ? pp->C : a.C;
   const T* const ob1 = pp ? pp->b1 : a.b1;
-  const T* const oH1 = pp ? pp->H1 : a.H1;
   const T* const obias = pp ? pp->bias : a.bias;
   const T* const oW3 = pp ? pp->W3 : a.W3;
   const T* const obias3 = pp ? pp->bias3 : a.bias3;
@@ -603,19 +599,6 @@ __device__ __forceinline__ void mm_body(const MMArgs<T>& a, const PR& pr, const 
     load_chunk<T, BOP, !TB, BV, MK>(bv[s], oB, a.ldb, n0, a.N, k0, ke, lr, lg, oms, ob1);
   };
   auto mfma = [&](int s, int k0) {
-    if constexpr (EPI == MM_L23 && AOP == OP_H1) {
-      // h1 of the k range of this WG's own column slice (one writer per element) for the kernels
-      // that need h1 after this forward (layer-1 backward gate, W2 gradient)
-      if (a.h1out) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int r = m0 + 16 * i + lr, k = k0 + kmap<T>(u, lg);
-            if (r < a.M && k < ke && k >= n0 && k < n0 + 32) a.h1out[(size_t)r * a.lda + k] = av[s][u][i];
-          }
-      }
-    }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -661,15 +644,8 @@ __device__ __forceinline__ void mm_body(const MMArgs<T>& a, const PR& pr, const 
       T g = T(0);
       if (m < a.M && n < a.N) {
         const size_t i = (size_t)m * a.ldc + n;
-        if (oH1) {
-          // (xw + b1)·m0 > 0 ⟺ h1 > 0, and then m0 = scale; where h1 = 0 the product is ±0 either way
-          // (the sign of v·0), so this is the reference's value without reading m0 again
-          const bool pos = oH1[i] > T(0);
-          g = (v * (pos ? T(1) : T(0))) * (pos ? oms.scale : T(0));
-        } else {
-          const T m0v = mval<T, MK>(oms, 0, i);
-          g = (v * ((a.H[i] + ob1[n]) * m0v > T(0) ? T(1) : T(0))) * m0v;
-        }
+        const T m0v = mval<T, MK>(oms, 0, i);
+        g = (v * ((a.H[i] + ob1[n]) * m0v > T(0) ? T(1) : T(0))) * m0v;
         oC[i] = g;
       }
       red[0][mm][nn] = g;
@@ -941,7 +917,6 @@ constexpr int FR_MAXP = 8;               // problems per launch: six sub-steps +
 template <typename T> struct RbFwdProb {
   const T* xw; const T* xw2;             // layer 1 as split-K planes: xw + xw2 (xw2 null: one plane)
   T* xwout;                              // the summed xw of the block's rows is stored here (null: not)
-  T* h1out;                              // h1 of the block's rows is stored here (null: not)
   const T* b1; const T* W2; const T* b2; const T* W3; const T* b3;
   MaskSrc<T> ms;
   T* ga2; T* pb2; T* pb3; T* pw3;        // outputs, null when not wanted; partials [⌈B/16⌉][…]
@@ -986,22 +961,12 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
   KArgs* ka = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const int pb = (int)blockIdx.y;
   struct {
-    const T *xw, *xw2; T *xwout, *h1out; const T *b1, *W2, *b2, *W3, *b3;
+    const T *xw, *xw2; T *xwout; const T *b1, *W2, *b2, *W3, *b3;
     const uint32_t* keep; const T* vals; T scale; int mn;
     T *ga2, *pb2, *pb3, *pw3; double* lpart;
-  } P = {ka->p[pb].xw, ka->p[pb].xw2, ka->p[pb].xwout, ka->p[pb].h1out, ka->p[pb].b1, ka->p[pb].W2, ka->p[pb].b2,
+  } P = {ka->p[pb].xw, ka->p[pb].xw2, ka->p[pb].xwout, ka->p[pb].b1, ka->p[pb].W2, ka->p[pb].b2,
          ka->p[pb].W3, ka->p[pb].b3, ka->p[pb].ms.keep, ka->p[pb].ms.vals, ka->p[pb].ms.scale, ka->p[pb].ms.mn,
          ka->p[pb].ga2, ka->p[pb].pb2, ka->p[pb].pb3, ka->p[pb].pw3, ka->p[pb].lpart};
-  // MK_PHILOX: the masks are drawn here, as the sampler's keep flags would hold them (flag e of forward f =
-  // bit e % 64 of keep_group(e / 64) under slot MASK_SLOT0 + f)
-  MaskSrc<T> pms{};
-  if constexpr (MK == MK_PHILOX) {
-    pms.mn = P.mn; pms.seed = ka->p[pb].ms.seed; pms.chain = ka->p[pb].ms.chain; pms.step = ka->p[pb].ms.step;
-    pms.slot = ka->p[pb].ms.slot;
-  }
-  auto pflags = [&](size_t e) {                               // flags e … e + 3 (e % 4 == 0) as 4 bits
-    return (philox_keep_word(pms, e) >> (e & 31)) & 0xFu;
-  };
   const MaskSrc<T> nomask{};
   const int rb = blockIdx.x, m0 = rb * FR_ROWS, nm = a.n_mid, No = a.n_out, M = a.M;
   auto stamp = [&](int ph) {
@@ -1070,28 +1035,12 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
       m2v4[j] = *reinterpret_cast<const float4*>(P.vals + (size_t)2 * mn + e);
     }
   }
-  if constexpr (MK == MK_PHILOX) {                            // drawn while the loads above are in flight
-#pragma unroll
-    for (int h = 0; h < HP; ++h) hk[h] = pflags(hbase[h]);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      k1[j] = pflags((size_t)mn + ebase[j]);
-      k2[j] = pflags((size_t)2 * mn + ebase[j]);
-    }
-    // pinned here, so the draws overlap the loads in flight instead of sinking into the epilogue
-#pragma unroll
-    for (int h = 0; h < HP; ++h) asm volatile("" : "+v"(hk[h]));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) asm volatile("" : "+v"(k1[j]), "+v"(k2[j]));
-  }
   const int32_t yv = a.y[min(m0 + (tid >> 4), M - 1)];
   const T b3v = P.b3[min(tid & 15, No - 1)];
   // h1 = max((xw + b1)·m0, 0) (mlp.py:30) and W3 into LDS
-  // the mask value of flag q of a 4-element piece at element e: one bit of a keep word (bit e % 32 + q), or
-  // bit q of the drawn flags
+  // the mask value of flag q of a 4-element piece at element e: one bit of a keep word (bit e % 32 + q)
   auto mbit = [&](uint32_t w, size_t e, int q) {
-    const uint32_t sh = MK == MK_PHILOX ? (uint32_t)q : (uint32_t)((e & 31) + q);
-    return ((w >> sh) & 1u) ? P.scale : T(0);
+    return ((w >> (uint32_t)((e & 31) + q)) & 1u) ? P.scale : T(0);
   };
 #pragma unroll
   for (int h = 0; h < HP; ++h) {
@@ -1107,12 +1056,10 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         T mk = T(1);
-        if constexpr (MK == MK_KEEP || MK == MK_PHILOX) mk = mbit(hk[h], hbase[h], q);
+        if constexpr (MK == MK_KEEP) mk = mbit(hk[h], hbase[h], q);
         if constexpr (MK == MK_VALS) mk = vv[q];
         At[rr][c + q] = ok ? op_apply<T, OP_H1>(x[q], mk, bb[q]) : T(0);
       }
-      if (P.h1out && ok)                                       // for the layer-1 backward's gate / the W2 gradient
-        *reinterpret_cast<float4*>(P.h1out + hbase[h]) = *reinterpret_cast<const float4*>(&At[rr][c]);
     }
     const int o = e / (FR_NMAX / 4), c3 = (e % (FR_NMAX / 4)) * 4;
     const bool ok3 = o < No && c3 < nm;
@@ -1158,7 +1105,7 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
       const int n = n0 + 16 * j + Mf::row(lane, q);
       const bool ok = rok && n < nm;
       m1v[j][q] = m2v[j][q] = T(1);
-      if constexpr (MK == MK_KEEP || MK == MK_PHILOX) {
+      if constexpr (MK == MK_KEEP) {
         m1v[j][q] = mbit(k1[j], (size_t)mn + ebase[j], q);
         m2v[j][q] = mbit(k2[j], (size_t)2 * mn + ebase[j], q);
       }
@@ -1572,7 +1519,6 @@ struct MlpNet {
   int B, n_in, n_mid, n_out, nlb;
   const T* X; const int32_t* y;
   T *xw, *h2, *d3, *z, *gz, *ga2, *ga1;
-  T* h1 = nullptr; bool h1_valid = false;   // h1 of the last fused forward (when its sub-step needs it)
   T *pb1, *pb2, *pb3, *pw3;              // gradient partials of b1, b2, b3, W3 ([nlb][...])
   T *fpb2 = nullptr, *fpb3 = nullptr, *fpw3 = nullptr;   // the same partials per 16-row block (k_fwdr, [nrb][...])
   unsigned long long* fr_prof = nullptr;  // HMCX_FWDR_PROF: stamps of the call's k_fwdr launches
@@ -1676,7 +1622,6 @@ hipError_t mm(MlpNet<T>& net, MMArgs<T>& a, const MMProbs<T>* prp = nullptr) {
   constexpr bool masked = AOP == OP_H1 || BOP == OP_H1 || EPI == MM_L2 || EPI == MM_L3CE || EPI == MM_GA1 ||
                           EPI == MM_L23;
   if constexpr (!masked) go(std::integral_constant<int, MK_NONE>{});
-  else if (a.ms.slot) go(std::integral_constant<int, MK_PHILOX>{});
   else if (a.ms.keep) go(std::integral_constant<int, MK_KEEP>{});
   else if (a.ms.vals) go(std::integral_constant<int, MK_VALS>{});
   else go(std::integral_constant<int, MK_NONE>{});
@@ -1689,7 +1634,7 @@ void mm_set(MMArgs<T>& a, int M, int N, int K, const T* A, int lda, int ta, cons
 }
 
 // What the layer-3 kernel produces besides the loss
-struct L3Want { bool ga2, pb2, pb3, pw3, h1 = false; };
+struct L3Want { bool ga2, pb2, pb3, pw3; };
 
 // Forward with masks `ms` at parameters q (+ the requested layer-3 backward pieces); loss partials
 // into lpart (null: no loss); logits (optional) stored without b3.  Layer 1 only when xw is stale.
@@ -1698,7 +1643,6 @@ hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double
                        T* logits = nullptr) {
   const int B = net.B, nm = net.n_mid;
   hipError_t e;
-  net.h1_valid = false;
   if (net.fwd_counts) ++net.fwd_counts[2];
   if (!net.xw_valid) {                                        // xw = X·W1ᵀ
     MMArgs<T> a{};
@@ -1718,8 +1662,6 @@ hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double
     a.pb3 = w.pb3 ? net.pb3 : nullptr;
     a.pw3 = w.pw3 ? net.pw3 : nullptr;
     a.C = nullptr; a.C2 = nullptr;                             // h2 / d3 stay in LDS
-    a.h1out = w.h1 ? net.h1 : nullptr;
-    net.h1_valid = w.h1;
     a.gx = net.gx; a.gx_bytes = net.gx_bytes; a.ep = gx_next_epoch(net.ctx); a.abort_flag = net.abort_flag;
     a.force_abort = net.l23_count == net.force_abort;
     if (net.prof && net.l23_count < net.prof_cap)
@@ -1759,8 +1701,7 @@ hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double
   a.pend = net.pend;
   net.pend.n = 0;
   const size_t lds = 32 * sizeof(double) + ((size_t)MM_NT + (size_t)32 * (net.n_out + 1)) * sizeof(T);
-  if (a.ms.slot) hipLaunchKernelGGL((k_l3_wide<T, MK_PHILOX>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
-  else if (a.ms.keep) hipLaunchKernelGGL((k_l3_wide<T, MK_KEEP>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
+  if (a.ms.keep) hipLaunchKernelGGL((k_l3_wide<T, MK_KEEP>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
   else if (a.ms.vals) hipLaunchKernelGGL((k_l3_wide<T, MK_VALS>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
   else hipLaunchKernelGGL((k_l3_wide<T, MK_NONE>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
   return hipGetLastError();
@@ -1771,7 +1712,6 @@ hipError_t mlp_ga1(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, bool want_
   MMArgs<T> a{};
   mm_set<T>(a, net.B, net.n_mid, net.n_mid, net.ga2, net.n_mid, 0, q[2], net.n_mid, 0, net.ga1, net.n_mid);
   a.ms = ms; a.H = net.xw; a.b1 = q[1];
-  a.H1 = net.h1_valid ? net.h1 : nullptr;
   a.colpart = want_pb1 ? net.pb1 : nullptr;
   return mm<T, MM_GA1, 0, 0>(net, a);
 }
@@ -1783,10 +1723,6 @@ hipError_t mlp_wgrad(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, int v, i
   MMArgs<T> a{};
   a.upd_mode = mode; a.u = u;
   if (v == 2) {                                               // ga2ᵀ·h1
-    if (net.h1_valid) {                                       // h1 stored by the fused forward
-      mm_set<T>(a, nm, nm, B, net.ga2, nm, 1, net.h1, nm, 0, nullptr, nm);
-      return mm<T, MM_UPD, 1, 0>(net, a);
-    }
     mm_set<T>(a, nm, nm, B, net.ga2, nm, 1, net.xw, nm, 0, nullptr, nm);
     a.ms = ms; a.b1 = q[1];
     return mm<T, MM_UPD, 1, 0, OP_PLAIN, OP_H1>(net, a);
@@ -1878,12 +1814,11 @@ void ga1_build(MlpNet<T>& net, const SubStep<T>* const* ss, int np, MMArgs<T>& a
     q = MMProb<T>{};
     q.A = s.scr->ga2; q.B = s.q[2]; q.C = s.scr->ga1;
     q.b1 = s.q[1]; q.ms = s.ms;
-    q.H1 = s.w.h1 ? s.scr->h1 : nullptr;                        // k_fwdr stored h1: the gate reads it alone
     q.colpart = s.v == 1 ? s.scr->pb1 : nullptr;
   }
   const MMProb<T>& q0 = pr.p[0];
   mm_set<T>(a, net.B, nm, nm, q0.A, nm, 0, q0.B, nm, 0, q0.C, nm);
-  a.ms = q0.ms; a.H = net.xw; a.b1 = q0.b1; a.H1 = nullptr; a.colpart = q0.colpart;
+  a.ms = q0.ms; a.H = net.xw; a.b1 = q0.b1; a.colpart = q0.colpart;
 }
 
 // Weight gradient of W1 (v = 0: ga1ᵀ·X) or W2 (v = 2: ga2ᵀ·h1) of sub-step net `sn` with the SGHMC
@@ -1914,7 +1849,7 @@ hipError_t mlp_forward_batch(MlpNet<T>& net, const SubStep<T>* ss, int np) {
 
 // mask kind of a launch (one per launch: every sub-grid reads the same kind)
 template <typename T> inline int mask_kind(const MaskSrc<T>& ms) {
-  return ms.slot ? MK_PHILOX : ms.keep ? MK_KEEP : ms.vals ? MK_VALS : MK_NONE;
+  return ms.keep ? MK_KEEP : ms.vals ? MK_VALS : MK_NONE;
 }
 
 // The layer-1 backwards of np sub-steps and the W2 gradient of sub-step net `w2n` in ONE launch
@@ -1949,7 +1884,6 @@ hipError_t mlp_ga1_w2(MlpNet<T>& net, const SubStep<T>* const* ss, int np, MlpNe
     else go(mkc, std::integral_constant<int, 0>{});
   };
   switch (mask_kind(a1.ms)) {
-    case MK_PHILOX: go_mk(std::integral_constant<int, MK_PHILOX>{}); break;
     case MK_KEEP: go_mk(std::integral_constant<int, MK_KEEP>{}); break;
     case MK_VALS: go_mk(std::integral_constant<int, MK_VALS>{}); break;
     default: go_mk(std::integral_constant<int, MK_NONE>{}); break;
@@ -2011,7 +1945,7 @@ bool fwdr_ok(const MlpNet<T>& net, const SubStep<T>* ss, int n) {
   // on a keep word
   if (net.n_in % 8 || net.B % 4 || ((size_t)(net.B / 4) * net.n_mid) % 32) return false;
   const int mk = mask_kind(ss[0].ms);
-  if (mk != MK_KEEP && mk != MK_VALS && mk != MK_PHILOX) return false;
+  if (mk != MK_KEEP && mk != MK_VALS) return false;
   for (int i = 0; i < n; ++i) {
     const T* xw = ss[i].xw ? ss[i].xw : net.xw;
     if (!vec_ok(xw, net.n_mid, sizeof(T)) || !vec_ok(ss[i].q[2], net.n_mid, sizeof(T)) || mask_kind(ss[i].ms) != mk)
@@ -2046,7 +1980,6 @@ hipError_t mlp_fwdr(MlpNet<T>& net, const SubStep<T>* const* ss, int np, const R
     q.xw = x.xw ? x.xw : net.xw;
     q.xw2 = x.xw2;
     q.xwout = x.xwout;
-    q.h1out = x.w.h1 ? x.scr->h1 : nullptr;
     q.b1 = x.q[1]; q.W2 = x.q[2]; q.b2 = x.q[3]; q.W3 = x.q[4]; q.b3 = x.q[5];
     q.ms = x.ms;
     q.ga2 = (x.v >= 0 && x.v <= 2) ? x.scr->ga2 : nullptr;
@@ -2062,8 +1995,7 @@ hipError_t mlp_fwdr(MlpNet<T>& net, const SubStep<T>* const* ss, int np, const R
   const dim3 grid((unsigned)net.nrb, (unsigned)(np + (a.pend.n > 0 ? 1 : 0)) + krows);
   if constexpr (sizeof(T) == 4) {                              // float32 only (fwdr_ok)
     const int mk = mask_kind(a.p[0].ms);
-    if (mk == MK_PHILOX) hipLaunchKernelGGL((k_fwdr<T, MK_PHILOX>), grid, dim3(FR_NW * 64), 0, net.st, a);
-    else if (mk == MK_KEEP) hipLaunchKernelGGL((k_fwdr<T, MK_KEEP>), grid, dim3(FR_NW * 64), 0, net.st, a);
+    if (mk == MK_KEEP) hipLaunchKernelGGL((k_fwdr<T, MK_KEEP>), grid, dim3(FR_NW * 64), 0, net.st, a);
     else hipLaunchKernelGGL((k_fwdr<T, MK_VALS>), grid, dim3(FR_NW * 64), 0, net.st, a);
     return hipGetLastError();
   }
@@ -2104,8 +2036,6 @@ hipError_t mlp_w1_w2split(MlpNet<T>& pn0, const SubStep<T>& s1, const Upd<T>& u1
   wgrad_build(w2n, s2, 2, Upd<T>{}, a2);
   a2.upd_mode = UPD_NONE;
   a2.pend.n = 0;
-  const bool h1 = s2.w.h1;                                     // B = the stored h1 (no xw / b1 / mask reads)
-  if (h1) a2.B = w2n.h1;
   const int nm = w2n.n_mid, Kq = w2n.B / 4;
   a2.K = Kq;
   p2.n = 4;
@@ -2116,7 +2046,6 @@ hipError_t mlp_w1_w2split(MlpNet<T>& pn0, const SubStep<T>& s1, const Upd<T>& u1
     x.ms = a2.ms;
     if (x.ms.keep) x.ms.keep += r0 / 32;
     if (x.ms.vals) x.ms.vals += r0;
-    if (h1) x.ms = MaskSrc<T>{};
   }
   a2.C = p2.p[0].C; a2.ldc = nm;
   const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, 1 + (a1.pend.n > 0 ? 1 : 0));
@@ -2128,11 +2057,6 @@ hipError_t mlp_w1_w2split(MlpNet<T>& pn0, const SubStep<T>& s1, const Upd<T>& u1
       hipLaunchKernelGGL((k_mm2b<T, MM_UPD, OP_PLAIN, OP_PLAIN, 1, 0, 0, 0, MM_STORE, OP_PLAIN, OP_H1, 1, 0, 0, 0, MK>),
                          grid, dim3(MM_NT), 0, pn0.st, a1, p1, a2, p2, g1, g2);
     };
-    if (h1) {
-      hipLaunchKernelGGL((k_mm2b<T, MM_UPD, OP_PLAIN, OP_PLAIN, 1, 0, 0, 0, MM_STORE, OP_PLAIN, OP_PLAIN, 1, 0, 0, 0, MK_NONE>),
-                         grid, dim3(MM_NT), 0, pn0.st, a1, p1, a2, p2, g1, g2);
-      return hipGetLastError();
-    }
     if (mask_kind(a2.ms) == MK_KEEP) go(std::integral_constant<int, MK_KEEP>{});
     else go(std::integral_constant<int, MK_VALS>{});
     return hipGetLastError();
@@ -2258,7 +2182,7 @@ int net_fuse(hmcx_ctx* ctx, MlpNet<T>& net, int regions = 1) {
   const int S = (net.n_mid + 31) / 32;
   if (off || ctx->mlp_nofuse || net.n_out > 32 || S > 16) return HMCX_OK;
   int per_cu = 0;
-  const void* kfn = (const void*)k_mm<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MK_PHILOX>;
+  const void* kfn = (const void*)k_mm<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MK_KEEP>;
   HMCX_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, MM_NT, 0));
   if ((long)per_cu * ctx->num_cus < (long)net.nlb * S) return HMCX_OK;
   const size_t need = (size_t)net.nlb * S * 32 * net.n_out * 16;
@@ -2269,9 +2193,7 @@ int net_fuse(hmcx_ctx* ctx, MlpNet<T>& net, int regions = 1) {
   for (const void* f : {(const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MK_KEEP>,
                         (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 0, 0, MK_KEEP>,
                         (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MK_VALS>,
-                        (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 0, 0, MK_VALS>,
-                        (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MK_PHILOX>,
-                        (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 0, 0, MK_PHILOX>}) {
+                        (const void*)k_mmb<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 0, 0, MK_VALS>}) {
     int pc = 0;
     if (int rc = kernel_occupancy(ctx, f, MM_NT, 0, &pc)) return rc;
     per_b = std::min(per_b, pc);
@@ -2294,7 +2216,7 @@ int net_fuse(hmcx_ctx* ctx, MlpNet<T>& net, int regions = 1) {
 template <typename T>
 void mlp_workspace(Workspace& ws, MlpNet<T>& net) {
   const size_t mn = (size_t)net.B * net.n_mid;
-  net.xw = ws.take<T>(mn); net.h2 = ws.take<T>(mn); net.d3 = ws.take<T>(mn); net.h1 = ws.take<T>(mn);
+  net.xw = ws.take<T>(mn); net.h2 = ws.take<T>(mn); net.d3 = ws.take<T>(mn);
   net.ga2 = ws.take<T>(mn); net.ga1 = ws.take<T>(mn);
   net.z = ws.take<T>((size_t)net.B * net.n_out); net.gz = ws.take<T>((size_t)net.B * net.n_out);
   net.pb1 = ws.take<T>((size_t)net.nlb * net.n_mid);
@@ -2325,7 +2247,7 @@ int mlp_grad_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, 
   double* lpart;
   do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
-  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid, 0, 0, 0, 0};
+  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid};
   if (masks && (uintptr_t)masks % 16) net.vec_masks = false;
   T* q[6];
   for (int v = 0; v < 6; ++v) q[v] = (T*)par->p[v];
@@ -2364,7 +2286,7 @@ int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
   do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
   const void* mptr = s->mask_mode == HMCX_MLP_MASKS_NONE ? nullptr : s->masks;
-  const MaskSrc<T> ms{(const T*)mptr, nullptr, T(1), s->B * s->n_mid, 0, 0, 0, 0};
+  const MaskSrc<T> ms{(const T*)mptr, nullptr, T(1), s->B * s->n_mid};
   if (mptr && (uintptr_t)mptr % 16) net.vec_masks = false;
   T *q[6], *p[6], *g[6];
   int64_t dim[6];
@@ -2458,7 +2380,7 @@ int mlp_loss_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, 
   double* lpart;
   do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
-  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid, 0, 0, 0, 0};
+  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid};
   if (masks && (uintptr_t)masks % 16) net.vec_masks = false;
   T* q[6];
   for (int v = 0; v < 6; ++v) q[v] = (T*)par->p[v];
@@ -2505,17 +2427,12 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     maxF = std::max(maxF, 6 * s->n_iter[si] + 2);
   }
   const bool philox_masks = s->mask_mode == HMCX_NOISE_PHILOX;
-  // Philox masks: the flags of a whole step stored once by k_mlp_keep and loaded by the kernels
-  // (default), or drawn inside the kernels where they are read (HMCX_MLP_MASKS=philox).  Measured on
-  // one box at config 3 (tools/gpu_r03_mlp_env.sh): 7.22 k leapfrog/s stored vs 6.38 k drawn — the
-  // draws sit on the layer-2 GEMM's critical path; stored h1 for the W1 / b1 / W2 backward
-  // (HMCX_MLP_H1=1) recovers most of it when drawn (6.76 k) and changes nothing when stored (7.19 k).
-  const char* mk_env = getenv("HMCX_MLP_MASKS");
-  const bool keep_arr = philox_masks && !(mk_env && !strcmp(mk_env, "philox"));
+  // A step's masks come from one of two sources: the caller's buffer (MK_VALS), or — Philox masks — the
+  // step's keep flags, drawn once (k_mlp_start / k_mlp_keep / k_fwdr's free rows) and loaded by every
+  // kernel that reads them (MK_KEEP).  No kernel here draws its own flags: the draws would sit on the
+  // layer-2 GEMM's critical path.
   const char* ks_env = getenv("HMCX_MLP_KEEP_SPLIT");
   const bool keep_split_on = !(ks_env && ks_env[0] == '0');
-  const char* h1_env = getenv("HMCX_MLP_H1");
-  const bool store_h1 = philox_masks && h1_env && h1_env[0] == '1';    // m0 ∈ {0, scale} only for Philox masks
   // Batched iterations.  Sub-step i of leapfrog iteration it (variable v = order[i]) evaluates the
   // gradient at q_u(it) for the variables at order positions u ≤ i and q_u(it − 1) for the others
   // (sghmc.py:29-34: each variable is drifted just before its own gradient call) and moves only v's
@@ -2528,7 +2445,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
   // HMCX_MLP_BATCH=0 runs the sub-steps one at a time.
   const char* batch_env = getenv("HMCX_MLP_BATCH");             // read per call (tests switch it)
   const bool batch_off = batch_env && batch_env[0] == '0';
-  const bool batch = !batch_off && net.fuse && s->order[0] == 0 && !store_h1 && net.l23_fit >= 1;
+  const bool batch = !batch_off && net.fuse && s->order[0] == 0 && net.l23_fit >= 1;
   MlpNet<T> pn[6]{};
   MlpNet<T> en[2]{};                                           // scratch (gz) of the E_new / E_current forwards
   if (philox_masks) {
@@ -2582,7 +2499,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     lp_cur = ws.take<double>(std::max(net.nlb, net.nrb));        // 32-row (k_mm) or 16-row (k_fwdr) partials
     lp_new = ws.take<double>(std::max(net.nlb, net.nrb));
     lp_scr = ws.take<double>(net.nlb);
-    if (keep_arr) keep = ws.take<uint32_t>((size_t)maxF * kw);
+    if (philox_masks) keep = ws.take<uint32_t>((size_t)maxF * kw);
     accf = ws.take<int32_t>(1);
   } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
@@ -2607,36 +2524,30 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     const int n = s->n_iter[si], F = 6 * n + 2;
     const uint32_t step_id = s->step_base + (uint32_t)si;
     const double* nz = s->noise_mode == HMCX_NOISE_BUFFER ? s->noise + s->noise_off[si] : nullptr;
-    // the k_fwdr path for this step's iterations (decided before the momentum launch: with Philox masks
-    // k_fwdr draws every mask itself, so the step's keep flags are not drawn at all)
+    // masks of forward f of the step: its stored keep flags (Philox), or the caller's values
+    auto masks_for = [&](int f) -> MaskSrc<T> {
+      if (philox_masks) return MaskSrc<T>{nullptr, keep + (size_t)f * kw, scale, mn};
+      return MaskSrc<T>{(const T*)s->masks + s->mask_off[si] + (size_t)f * n3, nullptr, scale, mn};
+    };
+    // the k_fwdr path for this step's iterations (decided before the momentum launch, which draws fewer
+    // keep flags when k_fwdr draws the later iterations')
     bool fr_step = false;
     if (batch && n > 0) {
       SubStep<T> chk[6];
       for (int i = 0; i < 6; ++i) {
         for (int j = 0; j < 6; ++j) chk[i].q[s->order[j]] = j <= i ? qa[s->order[j]] : par[s->order[j]];
         chk[i].xw = xw_par;
-        chk[i].ms = !philox_masks ? MaskSrc<T>{(const T*)s->masks + s->mask_off[si], nullptr, scale, mn, 0, 0, 0, 0}
-                    : keep_arr ? MaskSrc<T>{nullptr, keep, scale, mn, 0, 0, 0, 0}
-                               : MaskSrc<T>{nullptr, nullptr, scale, mn, s->seed, s->chain, step_id, MASK_SLOT0};
+        chk[i].ms = masks_for(0);
       }
       fr_step = fwdr_ok(net, chk, 6);
     }
-    // keep flags of every forward of the step in the momentum launch (compute-bound Philox draws: drawn
-    // instead beside each iteration's last launch, in an extra plane, they lengthened that launch by as
-    // much as they took off this one — 21.46 k vs 22.2 k leapfrog/s at config 3)
-    const bool fused_start = philox_masks && keep_arr;
+    // Philox masks: the keep flags of every forward of the step in the momentum launch (compute-bound Philox
+    // draws: drawn instead beside each iteration's last launch, in an extra plane, they lengthened that
+    // launch by as much as they took off this one — 21.46 k vs 22.2 k leapfrog/s at config 3).
     // On the k_fwdr path the step-start launch draws only iteration 0's flags and the two energy forwards';
     // each iteration's k_fwdr draws the next iteration's in rows of its own, on the CUs its problems leave free
     // (HMCX_MLP_KEEP_SPLIT=0: all at step start)
-    const bool keep_split = fused_start && fr_step && n > 1 && keep_split_on;
-    auto masks_for = [&](int f) -> MaskSrc<T> {
-      // PHILOX: the kernels draw the flags they read (MK_PHILOX, slot MASK_SLOT0 + f); with
-      // HMCX_MLP_MASKS=keep, k_mlp_keep stores the same flags once per step and the kernels load them
-      if (philox_masks && !keep_arr)
-        return MaskSrc<T>{nullptr, nullptr, scale, mn, s->seed, s->chain, step_id, MASK_SLOT0 + (uint32_t)f};
-      if (philox_masks) return MaskSrc<T>{nullptr, keep + (size_t)f * kw, scale, mn, 0, 0, 0, 0};
-      return MaskSrc<T>{(const T*)s->masks + s->mask_off[si] + (size_t)f * n3, nullptr, scale, mn, 0, 0, 0, 0};
-    };
+    const bool keep_split = philox_masks && fr_step && n > 1 && keep_split_on;
     // momentum (hmc.py:82-87), first drift into qa, Σp², Σθ² of the current state
     VarTab vt{};
     for (int i = 0; i < 6; ++i) {
@@ -2646,7 +2557,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     }
     const int32_t* prev_acc = commit_pending ? accf : nullptr;   // the previous step's commit, folded in
     commit_pending = false;
-    if (fused_start) {
+    if (philox_masks) {
       // forwards 0 … 5 and the energies 6n, 6n + 1 when split, else all F
       const KeepRange kr = keep_split ? KeepRange{8, 0, 6, 6 * n} : KeepRange{F, 0, F, 0};
       const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);        // one keep group per thread
@@ -2701,7 +2612,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
         x.ms = masks_for(6 * n + e);
         x.scr = &en[e];
         x.lpart = e == 0 ? lp_new : lp_cur;
-        x.w = L3Want{false, false, false, false, false};
+        x.w = L3Want{false, false, false, false};
         x.v = -1;
       }
       bool use_fr = false;                                     // the k_fwdr path (decided in iteration 0)
@@ -2722,7 +2633,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
           x.ms = masks_for(6 * it + i);
           x.scr = &pn[i];
           x.lpart = pn[i].lpart_scr;
-          x.w = L3Want{v <= 3, v == 3, v == 5, v == 4, false};
+          x.w = L3Want{v <= 3, v == 3, v == 5, v == 4};
           x.v = v;
           if (v <= 1) ga[nga++] = &ss[i];
         }
@@ -2760,9 +2671,6 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
           for (int i = 0; i < 6; ++i) {
             ss[i].xw = xwp[0];
             ss[i].xw2 = xwp[1];
-            // masks drawn inside k_fwdr (HMCX_MLP_MASKS=philox) live only there: it stores h1 for the W1 / b1
-            // gates and the W2 gradient
-            ss[i].w.h1 = philox_masks && !keep_arr && ss[i].v <= 2;
             fa[na++] = &ss[i];
           }
           ss[0].xwout = net.xw;
@@ -2877,8 +2785,7 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
         if (v == 0) net.xw_valid = false;
         const MaskSrc<T> ms = masks_for(fwd++);
         const Upd<T> u = upd_for(it, v, cur[v], it + 1 < n ? ((it & 1) ? qa[v] : qb[v]) : nullptr);
-        // h1 from the fused forward for the W1 / b1 / W2 sub-steps (HMCX_MLP_H1=0: recompute it)
-        const L3Want w{v <= 3, v == 3, v == 5, v == 4, store_h1 && v <= 2};
+        const L3Want w{v <= 3, v == 3, v == 5, v == 4};
         HMCX_HIP(ctx, mlp_forward<T>(net, cur, ms, lp_scr, w));
         if (v <= 1) HMCX_HIP(ctx, mlp_ga1<T>(net, cur, ms, v == 1));
         if (v == 0 || v == 2) HMCX_HIP(ctx, mlp_wgrad<T>(net, cur, ms, v, UPD_SGHMC, u));

@@ -1,6 +1,7 @@
-// hmcx_mlp_mask.h — the dropout masks of the MLP: where a forward's masks come from (MaskSrc), the Philox
-// keep flags (keep_group / keep_flags) and the per-kernel mask reads (mraw … mvals).  Shared by
-// hmcx_mlp.hip (gradient, loss, SGHMC) and hmcx_mlp_pred.hip (posterior predictive): one definition.
+// hmcx_mlp_mask.h — the dropout masks of the MLP: where a forward's masks come from (MaskSrc: the caller's
+// values or a step's stored keep flags), the Philox keep flags (keep_group / keep_flags) and the per-kernel
+// mask reads (mraw … mvals).  Shared by hmcx_mlp.hip (gradient, loss, SGHMC), whose kernels only ever load
+// masks, and hmcx_mlp_pred.hip (posterior predictive), whose kernel draws keep_group itself: one definition.
 #pragma once
 #include "hmcx_common.h"
 
@@ -12,13 +13,12 @@ constexpr uint32_t MASK_SLOT0 = 0x80000000u;
 // Dropout masks of one forward: m0, m1, m2 at offsets 0, mn, 2·mn.
 template <typename T> struct MaskSrc {
   const T* vals;          // explicit mask values (API / BUFFER mode), or
-  const uint32_t* keep;   // keep flags, one bit per element (bit e % 32 of word e / 32): value = keep ? scale : 0;
-                          // neither vals nor keep: no dropout or MK_PHILOX
+  const uint32_t* keep;   // keep flags, one bit per element (bit e % 32 of word e / 32): value = keep ? scale : 0
+                          // (Philox mode: element e = which·mn + i of forward f is bit e % 64 of keep_group(e / 64)
+                          // under slot MASK_SLOT0 + f, stored once per step — the values hmcx_mlp_masks gives);
+                          // neither vals nor keep: no dropout
   T scale;
   int mn;
-  // MK_PHILOX: the keep flags are drawn where they are used — element e = which·mn + i is bit e % 64 of
-  // keep_group(e / 64) under (seed, slot, step, chain), the values k_mlp_start and hmcx_mlp_masks give
-  uint64_t seed; uint32_t chain, step, slot;
 };
 
 // Dropout keep flags (Chainer, mlp.py:30-31: keep iff u >= ratio 0.1, u a 24-bit float32 uniform — keep iff
@@ -91,16 +91,11 @@ __device__ inline void keep_flags(uint32_t* keep, int n3, KeepRange kr, uint64_t
   if (2 * G + 1 < W) dst[1] = hi;
 }
 
-// the keep word (32 flags) holding element e of a MK_PHILOX source: bit e % 32
-template <typename T> __device__ inline uint32_t philox_keep_word(const MaskSrc<T>& s, size_t e) {
-  const KeepGroup g = keep_group(s.seed, (uint32_t)(e >> 6), s.slot, s.step, s.chain);
-  return (e & 32) ? g.hi : g.lo;
-}
-
 // Where the masks come from is a compile-time parameter (MK) of every kernel that reads them, so a
-// mask read is one load of the one source (MK_KEEP / MK_VALS), a Philox draw (MK_PHILOX) or nothing.
-// Loaded values are pinned by an empty asm after the batch they belong to, so hipcc cannot sink
-// a load into a branch (which it then waits for on the spot).
+// mask read is one load of the one source (MK_KEEP / MK_VALS) or nothing.  Loaded values are pinned by
+// an empty asm after the batch they belong to, so hipcc cannot sink a load into a branch (which it then
+// waits for on the spot).  MK_PHILOX tags the predictive kernel alone (hmcx_mlp_pred.hip), which draws
+// its flags with keep_group; mraw … mvals have no such case.
 enum MaskKind { MK_NONE = 0, MK_KEEP = 1, MK_VALS = 2, MK_PHILOX = 3 };
 template <typename T> struct MRaw { T v; uint32_t k; };
 template <typename T, int MK> __device__ inline MRaw<T> mraw(const MaskSrc<T>& s, int which, size_t i) {
@@ -108,7 +103,6 @@ template <typename T, int MK> __device__ inline MRaw<T> mraw(const MaskSrc<T>& s
   const size_t e = (size_t)which * s.mn + i;
   if constexpr (MK == MK_KEEP) r.k = (s.keep[e >> 5] >> (e & 31)) & 1u;
   if constexpr (MK == MK_VALS) r.v = s.vals[e];
-  if constexpr (MK == MK_PHILOX) r.k = (philox_keep_word(s, e) >> (e & 31)) & 1u;
   return r;
 }
 template <typename T, int MK> __device__ inline void mpin(MRaw<T>& r) {
@@ -116,7 +110,7 @@ template <typename T, int MK> __device__ inline void mpin(MRaw<T>& r) {
   if constexpr (MK == MK_VALS) asm volatile("" : "+v"(r.v));
 }
 template <typename T, int MK> __device__ inline T mfin(const MaskSrc<T>& s, const MRaw<T>& r) {
-  if constexpr (MK == MK_KEEP || MK == MK_PHILOX) return r.k ? s.scale : T(0);
+  if constexpr (MK == MK_KEEP) return r.k ? s.scale : T(0);
   else if constexpr (MK == MK_VALS) return r.v;
   else return T(1);
 }
@@ -140,10 +134,6 @@ template <typename T, int V, int MK> __device__ inline void mvals(const MaskSrc<
     uint32_t k = s.keep[e >> 5];                                 // e % V == 0: V bits of one word
     asm volatile("" : "+v"(k));
     k >>= (e & 31);
-#pragma unroll
-    for (int q = 0; q < V; ++q) m[q] = ((k >> q) & 1u) ? s.scale : T(0);
-  } else if constexpr (MK == MK_PHILOX) {                        // e % V == 0: V bits of one keep word
-    const uint32_t k = philox_keep_word(s, e) >> (e & 31);
 #pragma unroll
     for (int q = 0; q < V; ++q) m[q] = ((k >> q) & 1u) ? s.scale : T(0);
   } else {

@@ -425,28 +425,39 @@ def test_api_masks_equal_host_keep_groups(B, n_mid):
     assert set(np.unique(got)) <= {np.float32(0), np.float32(1 / 0.9)}
 
 
-@pytest.mark.parametrize("variant", ["keep", "philox-h1"])
-def test_sampler_philox_masks_equal_api_masks(variant, monkeypatch):
-    """In Philox mode the sampler's dropout flags — stored once per step by k_mlp_keep (default) or
-    drawn inside the kernels where they are read (HMCX_MLP_MASKS=philox, with the backward reading
-    the stored h1 instead of the masks, HMCX_MLP_H1=1) — are the values hmcx_mlp_masks gives for the
-    same (seed, chain, step, slot): a run fed those API masks as buffers follows the Philox-mask run
-    bit for bit (float64, Philox noise in both)."""
-    if variant == "philox-h1":
-        monkeypatch.setenv("HMCX_MLP_MASKS", "philox")
-        monkeypatch.setenv("HMCX_MLP_H1", "1")
+@pytest.mark.parametrize("variant", ["keep", "fwdr-f32"])
+def test_sampler_philox_masks_equal_api_masks(variant):
+    """In Philox mode the sampler's dropout flags, stored once per step (k_mlp_start / k_mlp_keep and,
+    on the k_fwdr path, the free rows of each iteration's k_fwdr) and loaded by every kernel that reads
+    them, are the values hmcx_mlp_masks gives for the same (seed, chain, step, slot): a run fed those
+    API masks as buffers follows the Philox-mask run bit for bit (Philox noise in both).
+    keep: config-3 shape in float64 (the k_mm forwards).  fwdr-f32: the 40-96-16 / B = 36 fixture shape
+    in float32, which k_fwdr takes (three column waves, row blocks 16 + 16 + 4, n_out at the limit), with
+    trajectories of two and more iterations — the step-start draw, the flags drawn in k_fwdr's free
+    rows for iterations ≥ 1 and both energy forwards all occur — and one k_fwdr launch per leapfrog
+    iteration in both runs."""
     from dropout_hamiltonian_montecarlo_amd import _native as nat
     mlp, sghmc = _mlp_cls()
-    n_in, n_mid, n_out, N, B = 784, 256, 10, 1000, 500
-    rs = np.random.RandomState(5)
-    X = rs.rand(N, n_in)
-    y = rs.randint(0, n_out, N)
-    m = mlp({"alpha": 0.01}, n_in, n_mid, n_out, dtype=torch.float64, device="cuda:0")
-    start = m.init_params(4)
-    kw = dict(path_length=3e-3, step_size=1e-3, verbose=False, noise='philox', seed=5, chain=3)
+    if variant == "keep":
+        n_in, n_mid, n_out, N, B = 784, 256, 10, 1000, 500
+        rs = np.random.RandomState(5)
+        X = rs.rand(N, n_in)
+        y = rs.randint(0, n_out, N)
+        dtype, min_L = torch.float64, 2
+        m = mlp({"alpha": 0.01}, n_in, n_mid, n_out, dtype=dtype, device="cuda:0")
+        start = m.init_params(4)
+        kw = dict(path_length=3e-3, step_size=1e-3, verbose=False, noise='philox', seed=5, chain=3)
+    else:
+        import _mlp_fixtures as fx
+        f = fx.BY_NAME["w96_b36"]
+        n_in, n_mid, n_out, B = f.n_in, f.n_mid, f.n_out, f.B
+        X, y, start = fx.problem(n_in, n_mid, n_out, B, n_batches=2)      # N = 72 rows
+        dtype, min_L = torch.float32, 3
+        m = mlp({"alpha": 0.01}, n_in, n_mid, n_out, dtype=dtype, device="cuda:0")
+        kw = dict(path_length=5e-3, step_size=1e-3, verbose=False, noise='philox', seed=5, chain=3)
 
     def api_masks(k, n):
-        out = torch.empty((n, 3, B, n_mid), dtype=torch.float64, device="cuda:0")
+        out = torch.empty((n, 3, B, n_mid), dtype=dtype, device="cuda:0")
         for f in range(n):
             m.ctx.check(m.ctx.lib.hmcx_mlp_masks(m.ctx.h, m.code, B, n_mid, 5, 3, k & 0xFFFFFFFF,
                                                  (nat.MLP_MASK_SLOT0 + f) & 0xFFFFFFFF, nat.ptr(out[f])),
@@ -458,10 +469,15 @@ def test_sampler_philox_masks_equal_api_masks(variant, monkeypatch):
         s = sghmc(m, start, **kw)
         s.mask_provider = provider
         s.trace, s.out = [], io.StringIO()
+        c0 = m.ctx.mlp_forward_counts()
         post, _ = s.sample(epochs=2, burnin=1, batch_size=B, X_train=X, y_train=y)
+        c1 = m.ctx.mlp_forward_counts()
         runs.append((post, [t["L"] for t in s.trace], [t["accepted"] for t in s.trace]))
+        if variant == "fwdr-f32":                                  # one k_fwdr launch per leapfrog iteration
+            assert c1["fwdr"] - c0["fwdr"] == sum(int(t["L"]) - 1 for t in s.trace) > 0
+            assert c1["batched"] == c0["batched"]
     (p1, L1, a1), (p2, L2, a2) = runs
-    assert L1 == L2 and a1 == a2 and max(L1) >= 2
+    assert L1 == L2 and a1 == a2 and max(L1) >= min_L
     for k in p1:
         np.testing.assert_array_equal(p1[k], p2[k])
 
