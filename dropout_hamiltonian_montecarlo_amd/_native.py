@@ -113,6 +113,25 @@ class HmcChainsArgs(ctypes.Structure):
                 ("out_nlp", c_void_p), ("out_E", c_void_p), ("out_trace", c_void_p), ("out_mom", c_void_p)]
 
 
+class MhArgs(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("model", c_int), ("B", c_int), ("D", c_int), ("K", c_int), ("C", c_int),
+                ("n_steps", c_int), ("alpha", c_double), ("log_prior", c_double), ("lp_const", c_double * 2),
+                ("X", c_void_p), ("Y", c_void_p), ("mult", c_dblp), ("site", c_i32p), ("u_accept", c_dblp),
+                ("noise_mode", c_int), ("noise", c_void_p), ("noise_off", c_i64p),
+                ("seed", ctypes.c_uint64), ("chain0", ctypes.c_uint32), ("step_base", ctypes.c_uint32),
+                ("W", c_void_p), ("b", c_void_p), ("out_A", c_void_p), ("out_accepted", c_void_p),
+                ("out_logp", c_void_p), ("out_E", c_void_p), ("out_trace", c_void_p)]
+
+
+class MhMvnArgs(ctypes.Structure):
+    _fields_ = [("dim", c_int), ("C", c_int), ("n_steps", c_int), ("mu", c_void_p), ("prec", c_void_p),
+                ("nlp_const", c_double), ("mult", c_dblp), ("site", c_i32p), ("u_accept", c_dblp),
+                ("noise_mode", c_int), ("noise", c_void_p), ("noise_off", c_i64p),
+                ("seed", ctypes.c_uint64), ("chain0", ctypes.c_uint32), ("step_base", ctypes.c_uint32),
+                ("x", c_void_p), ("out_A", c_void_p), ("out_accepted", c_void_p), ("out_logp", c_void_p),
+                ("out_E", c_void_p), ("out_trace", c_void_p)]
+
+
 MODEL_SOFTMAX, MODEL_LOGISTIC = 0, 1
 MLP_MASK_SLOT0 = 0x80000000
 MLP_MASKS_NONE, MLP_MASKS_FIXED, MLP_MASKS_PHILOX = 0, 1, 2
@@ -125,7 +144,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_softmax_grad", "hmcx_softmax_loglik", "hmcx_softmax_predict", "hmcx_sghmc_run",
            "hmcx_sgld_run", "hmcx_hmc_mvn_run", "hmcx_mlp_masks", "hmcx_mlp_grad", "hmcx_mlp_loss",
            "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_predictive", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
-           "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_axpy", "hmcx_mvn_eval",
+           "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics")
@@ -221,6 +240,9 @@ def load_library():
         lib.hmcx_hmc_run.argtypes = [c_void_p, ctypes.POINTER(HmcArgs)]
         if hasattr(lib, "hmcx_hmc_chains_run"):        # absent in older builds loaded for A/B runs
             lib.hmcx_hmc_chains_run.argtypes = [c_void_p, ctypes.POINTER(HmcChainsArgs)]
+        if hasattr(lib, "hmcx_mh_run"):                # absent in older builds loaded for A/B runs
+            lib.hmcx_mh_run.argtypes = [c_void_p, ctypes.POINTER(MhArgs)]
+            lib.hmcx_mh_mvn_run.argtypes = [c_void_p, ctypes.POINTER(MhMvnArgs)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
         lib.hmcx_mvn_eval.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                       c_void_p]

@@ -424,6 +424,85 @@ int hmc_mvn_run(hmcx_ctx* ctx, const hmcx_hmc_mvn_args* s) {
   return HMCX_OK;
 }
 
+// ------------------------------------------------------------------ MVN random-walk Metropolis
+// cpu/metropolis.py:27-64 with E = nlp(x) (mvn_gaussian.py:22-31): one thread per chain, all steps in
+// one launch, state and proposal in registers; E of the kept state is carried, not recomputed.
+struct MhMvnArgs {
+  MvnArgs m;                               // dim, C, n_steps, mu, prec, nlp_const, noise, x, out_A, out_acc, out_trace
+  const double* mult; const int32_t* site; // device [n_steps*C]
+  double* out_logp; double* out_E;
+};
+
+__global__ void k_mh_mvn(MhMvnArgs b) {
+  const MvnArgs& a = b.m;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= a.C) return;
+  double x[MVN_MAXDIM], xn[MVN_MAXDIM];
+  for (int j = 0; j < a.dim; ++j) x[j] = a.x[c * a.dim + j];
+  double E = mvn_nlp(a, x);
+  for (int s = 0; s < a.n_steps; ++s) {
+    const size_t sc = (size_t)s * a.C + c;
+    const double mult = b.mult[sc];
+    const int site = b.site[sc];
+    for (int j = 0; j < a.dim; ++j) {
+      xn[j] = x[j];
+      if (site >= 0 && site != j) continue;
+      double z;
+      if (a.noise_mode == HMCX_NOISE_BUFFER) z = a.noise[a.noff[sc] + j];
+      else z = philox_normal_d(a.seed, a.chain0 + c, a.step_base + s, 0u, (uint32_t)j);
+      xn[j] = x[j] + mult * z;                           // metropolis.py:59 / :62
+    }
+    const double Enew = mvn_nlp(a, xn);
+    const double A = exp(E - Enew);                      // metropolis.py:42
+    const int acc = isfinite(A) && a.u[sc] < A;          // metropolis.py:44: inf and NaN reject
+    a.out_A[sc] = A;
+    a.out_acc[sc] = acc;
+    if (b.out_E) { b.out_E[2 * sc] = E; b.out_E[2 * sc + 1] = Enew; }
+    if (acc) {
+      for (int j = 0; j < a.dim; ++j) x[j] = xn[j];
+      E = Enew;
+    }
+    b.out_logp[sc] = -E;
+    if (a.out_trace)
+      for (int j = 0; j < a.dim; ++j) a.out_trace[sc * a.dim + j] = x[j];
+  }
+  for (int j = 0; j < a.dim; ++j) a.x[c * a.dim + j] = x[j];
+}
+
+int mh_mvn_run(hmcx_ctx* ctx, const hmcx_mh_mvn_args* s) {
+  if (s->dim < 1 || s->dim > MVN_MAXDIM) return set_error(ctx, HMCX_EUNSUPPORTED, "mvn: dim must be 1..16");
+  const size_t nsc = (size_t)s->n_steps * s->C;
+  const bool buffer = s->noise_mode == HMCX_NOISE_BUFFER;
+  const void* hsrc[4] = {s->mult, s->site, s->u_accept, buffer ? s->noise_off : nullptr};
+  const size_t hbytes[4] = {nsc * sizeof(double), nsc * sizeof(int32_t), nsc * sizeof(double),
+                            buffer ? nsc * sizeof(int64_t) : 0};
+  Workspace ws(ctx);
+  char *sched, *dp[4];
+  do {
+    ws.reset();
+    sched = ws.take<char>(packed_bytes(4, hbytes));
+  } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  begin_call(ctx);
+  int rc = upload_packed(ctx, sched, 4, hsrc, hbytes, dp);
+  if (rc) return rc;
+  if ((rc = timing_begin(ctx, ctx->stream))) return rc;
+  MhMvnArgs b{};
+  MvnArgs& a = b.m;
+  a.dim = s->dim; a.C = s->C; a.n_steps = s->n_steps;
+  a.mu = s->mu; a.prec = s->prec; a.nlp_const = s->nlp_const;
+  b.mult = reinterpret_cast<const double*>(dp[0]);
+  b.site = reinterpret_cast<const int32_t*>(dp[1]);
+  a.u = reinterpret_cast<const double*>(dp[2]);
+  a.noise_mode = s->noise_mode; a.noise = s->noise; a.noff = reinterpret_cast<const int64_t*>(dp[3]);
+  a.seed = s->seed; a.chain0 = s->chain0; a.step_base = s->step_base;
+  a.x = s->x; a.out_A = s->out_A; a.out_acc = s->out_accepted; a.out_trace = s->out_trace;
+  b.out_logp = s->out_logp; b.out_E = s->out_E;
+  hipLaunchKernelGGL(k_mh_mvn, dim3((s->C + 63) / 64), dim3(64), 0, ctx->stream, b);
+  HMCX_HIP(ctx, hipGetLastError());
+  return timing_end(ctx, ctx->stream);
+}
+
 // An event behind the copies into an out_host block (one reusable, non-timing event per block).
 static int host_mark(hmcx_ctx* ctx, const void* out_host) {
   hipEvent_t ev = nullptr;
@@ -916,6 +995,48 @@ int hmcx_hmc_mvn_run(hmcx_ctx* ctx, const hmcx_hmc_mvn_args* a) {
     return set_error(ctx, HMCX_EINVAL, "BUFFER noise mode needs noise and noise_off");
   if (a->n_steps == 0) return HMCX_OK;
   return hmc_mvn_run(ctx, a);
+}
+
+int hmcx_mh_run(hmcx_ctx* ctx, const hmcx_mh_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  if (a->model != HMCX_MODEL_SOFTMAX && a->model != HMCX_MODEL_LOGISTIC)
+    return set_error(ctx, HMCX_EINVAL, "mh: model must be HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC");
+  if (a->model == HMCX_MODEL_LOGISTIC && a->K != 1) return set_error(ctx, HMCX_EINVAL, "mh: logistic needs K = 1");
+  int rc = check_dims(ctx, a->dtype, a->B, a->D, a->K, a->C);
+  if (rc) return rc;
+  if (a->C > 65535) return set_error(ctx, HMCX_EUNSUPPORTED, "mh: more than 65535 chains");
+  if ((long long)a->D * a->K + a->K > 0x7fffffffLL) return set_error(ctx, HMCX_EUNSUPPORTED, "too many parameters");
+  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "n_steps < 0");
+  if (a->n_steps == 0) return HMCX_OK;
+  if (!a->X || !a->Y || !a->W || !a->b || !a->mult || !a->site || !a->u_accept || !a->out_A || !a->out_accepted ||
+      !a->out_logp)
+    return set_error(ctx, HMCX_EINVAL, "null pointer");
+  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
+    return set_error(ctx, HMCX_EINVAL, "BUFFER noise needs noise and noise_off");
+  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "bad noise_mode");
+  const int dims[2] = {a->D * a->K, a->K};
+  for (size_t i = 0; i < (size_t)a->n_steps * a->C * 2; ++i)
+    if (a->site[i] < -1 || a->site[i] >= dims[i & 1]) return set_error(ctx, HMCX_EINVAL, "mh: site out of range");
+  return a->dtype == HMCX_F64 ? mh_run_t<double>(ctx, a) : mh_run_t<float>(ctx, a);
+}
+
+int hmcx_mh_mvn_run(hmcx_ctx* ctx, const hmcx_mh_mvn_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  if (!a->mu || !a->prec || !a->x || !a->mult || !a->site || !a->u_accept || !a->out_A || !a->out_accepted ||
+      !a->out_logp)
+    return set_error(ctx, HMCX_EINVAL, "mh_mvn: null pointer");
+  if (a->C < 1 || a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mh_mvn: bad sizes");
+  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
+    return set_error(ctx, HMCX_EINVAL, "BUFFER noise needs noise and noise_off");
+  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "bad noise_mode");
+  for (size_t i = 0; i < (size_t)a->n_steps * a->C; ++i)
+    if (a->site[i] < -1 || a->site[i] >= a->dim) return set_error(ctx, HMCX_EINVAL, "mh_mvn: site out of range");
+  if (a->n_steps == 0) return HMCX_OK;
+  return mh_mvn_run(ctx, a);
 }
 
 static int check_mlp(hmcx_ctx* ctx, int dtype, int B, int n_in, int n_mid, int n_out) {

@@ -241,6 +241,8 @@ template <typename T> int sgd_run_t(hmcx_ctx*, const hmcx_sgd_args*);
 template <typename T> int sumsq_t(hmcx_ctx*, const void*, int64_t, double*);
 template <typename T> int sghmc_run_t(hmcx_ctx*, const hmcx_sampler_args*);
 template <typename T> int hmc_chains_run_t(hmcx_ctx*, const hmcx_hmc_chains_args*);   // C ≥ 1 chains, one call
+template <typename T> int mh_run_t(hmcx_ctx*, const hmcx_mh_args*);                    // random-walk Metropolis
+int mh_mvn_run(hmcx_ctx*, const hmcx_mh_mvn_args*);
 template <typename T> int axpy_t(hmcx_ctx*, int, int64_t, double, const void*, void*);
 bool sghmc_p2_selected(hmcx_ctx*, const hmcx_sampler_args*);   // hmcx_softmax.hip
 template <typename T> int sgld_run_t(hmcx_ctx*, const hmcx_sampler_args*);

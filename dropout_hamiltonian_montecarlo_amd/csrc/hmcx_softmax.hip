@@ -1255,6 +1255,253 @@ int hmc_chains_run_t(hmcx_ctx* ctx, const hmcx_hmc_chains_args* s) {
   return timing_end(ctx, ctx->stream);
 }
 
+// ------------------------------------------------------------------ random-walk Metropolis, linear models
+// metropolis.py:27-64 with the softmax / logistic model, C chains in one call, state and proposal in the
+// [D][C·K] / [C·K] layout of the HMC chains.  A step costs one forward pass and no gradient, so the
+// elementwise work is one pass per step:
+//   k_mh_propose   q := previous proposal where that chain accepted, the previous step's trace row, the
+//                  new proposal q + mult·z (both variables) and its Σθ² partials       grid (nPB, C)
+//   k_fwd(FWD_LL)  log-likelihood of the proposals, all chains
+//   k_mh_accept    E, E_new, A = exp(E − E_new), accept iff finite and u < A; MhState per chain carries
+//                  the kept state's (ll, Σθ²) to the next step                          grid (C)
+// and one k_mh_commit after the last step (its trace row, the final state).
+struct MhState {
+  double ll, sW, sb;   // log-likelihood and Σθ² (weights, bias) of the current state q
+};
+
+constexpr int MH_EPB = 1024;   // weight elements per k_mh_propose block (a whole number of features)
+
+template <typename T>
+struct MhProposeArgs {
+  int D, K, C, N, P, nPB, fpb, logistic;   // fpb: features per block
+  const int32_t* prev_acc;                 // device [C] flags of the previous step, or null (step 0)
+  const double* mult; const int32_t* site; // device [C][2] rows of this step
+  int noise_mode; const double* noise; const int64_t* noff;   // noff: device [C] row of this step
+  uint64_t seed; uint32_t chain0, step;
+  T* W; T* b; T* Wn; T* bn;
+  T* trace;                                // [C][P] row of the PREVIOUS step, or null
+  double* sq_part;                         // [nPB + 1][C]: Σ Wn² per block, then Σ bn² (logistic only)
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_mh_propose(MhProposeArgs<T> a) {
+  __shared__ double ssh[256];
+  const int tid = threadIdx.x, K = a.K, c = blockIdx.y;
+  const int DK = a.D * K;
+  const int e0 = blockIdx.x * a.fpb * K, ne = min(a.fpb * K, DK - e0);
+  const bool buffer = a.noise_mode == HMCX_NOISE_BUFFER;
+  const int64_t noff = buffer ? a.noff[c] : 0;
+  const bool take = a.prev_acc && a.prev_acc[c] != 0;
+  const T mW = (T)a.mult[2 * c], mb = (T)a.mult[2 * c + 1];
+  const int sW = a.site[2 * c], sb = a.site[2 * c + 1];
+  auto draw = [&](int i) {
+    return buffer ? (T)a.noise[noff + i] : philox_normal_t<T>(a.seed, a.chain0 + c, a.step, 0u, (uint32_t)i);
+  };
+  double sq = 0.0;
+  for (int e = tid; e < ne; e += 256) {
+    const int i = e0 + e;
+    const size_t w = (size_t)(i / K) * a.N + c * K + i % K;
+    const T v = take ? a.Wn[w] : a.W[w];   // one read of the chain's state: the kept one
+    if (take) a.W[w] = v;
+    if (a.trace) a.trace[(size_t)c * a.P + i] = v;
+    T vn = v;
+    if (sW < 0 || sW == i) vn = v + mW * draw(i);
+    a.Wn[w] = vn;
+    sq += (double)vn * (double)vn;
+  }
+  if (a.logistic) {
+    ssh[tid] = sq;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) ssh[tid] += ssh[tid + s];
+      __syncthreads();
+    }
+    if (tid == 0) a.sq_part[(size_t)blockIdx.x * a.C + c] = ssh[0];
+  }
+  if (blockIdx.x == 0) {                   // the bias: K ≤ 256 elements
+    double qb = 0.0;
+    for (int k = tid; k < K; k += 256) {
+      const int j = c * K + k;
+      const T v = take ? a.bn[j] : a.b[j];
+      if (take) a.b[j] = v;
+      if (a.trace) a.trace[(size_t)c * a.P + DK + k] = v;
+      T vn = v;
+      if (sb < 0 || sb == k) vn = v + mb * draw(DK + k);
+      a.bn[j] = vn;
+      qb += (double)vn * (double)vn;
+    }
+    if (a.logistic) {
+      __syncthreads();
+      ssh[tid] = qb;
+      __syncthreads();
+      for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) ssh[tid] += ssh[tid + s];
+        __syncthreads();
+      }
+      if (tid == 0) a.sq_part[(size_t)a.nPB * a.C + c] = ssh[0];
+    }
+  }
+}
+
+template <typename T>
+struct MhAcceptArgs {
+  int D, K, C, N, nRB, nPB, first, logistic;
+  const double* u;                                             // device [C] row of this step
+  double log_prior, lpc0, lpc1, half_alpha;
+  const double* ll0_part; const double* ll1_part; const double* sq_part;
+  const T* W; const T* b;
+  MhState* st;                                                 // [C]
+  double* out_A; int32_t* out_acc; double* out_logp; double* out_E;   // [C] rows of this step
+};
+
+// Chain blockIdx.x: every sum in a fixed order (block_sum256).
+template <typename T>
+__global__ __launch_bounds__(256) void k_mh_accept(MhAcceptArgs<T> a) {
+  __shared__ double sh[256];
+  const int c = blockIdx.x, K = a.K, DK = a.D * K, C = a.C;
+  double ll0, sW0 = 0.0, sb0 = 0.0;
+  if (a.first) {
+    ll0 = block_sum256(a.nRB, [&](int i) { return a.ll0_part[(size_t)i * C + c]; }, sh);
+    if (a.logistic) {
+      sW0 = block_sum256(DK, [&](int i) { const double v = (double)a.W[(size_t)(i / K) * a.N + c * K + i % K]; return v * v; }, sh);
+      sb0 = block_sum256(K, [&](int i) { const double v = (double)a.b[c * K + i]; return v * v; }, sh);
+    }
+  } else {
+    ll0 = a.st[c].ll; sW0 = a.st[c].sW; sb0 = a.st[c].sb;
+  }
+  const double ll1 = block_sum256(a.nRB, [&](int i) { return a.ll1_part[(size_t)i * C + c]; }, sh);
+  double sW1 = 0.0, sb1 = 0.0;
+  if (a.logistic) {
+    sW1 = block_sum256(a.nPB, [&](int i) { return a.sq_part[(size_t)i * C + c]; }, sh);
+    sb1 = a.sq_part[(size_t)a.nPB * C + c];
+  }
+  if (threadIdx.x == 0) {
+    auto logp = [&](double ll, double sW, double sb) {
+      double lp = a.log_prior;                                   // softmax.py:22-30 (constant)
+      if (a.logistic) lp = (((0.0 + a.lpc0) - a.half_alpha * sW) + a.lpc1) - a.half_alpha * sb;   // logistic.py:15-21
+      return ll + lp;
+    };
+    const double lp0 = logp(ll0, sW0, sb0), lp1 = logp(ll1, sW1, sb1);
+    const double Ecur = -lp0, Enew = -lp1;                       // metropolis.py:49-50
+    const double A = exp(Ecur - Enew);                           // metropolis.py:42
+    const int acc = isfinite(A) && a.u[c] < A;                   // metropolis.py:44: inf and NaN reject
+    a.out_A[c] = A;
+    a.out_acc[c] = acc;
+    if (a.out_E) { a.out_E[2 * c] = Ecur; a.out_E[2 * c + 1] = Enew; }
+    MhState s;
+    if (acc) { s.ll = ll1; s.sW = sW1; s.sb = sb1; }
+    else { s.ll = ll0; s.sW = sW0; s.sb = sb0; }
+    a.st[c] = s;
+    a.out_logp[c] = acc ? lp1 : lp0;
+  }
+}
+
+// After the last step: q := proposal for the chains that accepted; trace [C][P] row of the kept states.
+template <typename T>
+__global__ __launch_bounds__(256) void k_mh_commit(int D, int K, int N, const int32_t* acc, const T* Wn, const T* bn,
+                                                   T* W, T* b, T* trace) {
+  const int c = blockIdx.y, DK = D * K, P = DK + K;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool take = acc[c] != 0;
+  if (!take && !trace) return;
+  if (i < DK) {
+    const size_t w = (size_t)(i / K) * N + c * K + i % K;
+    T v = W[w];
+    if (take) { v = Wn[w]; W[w] = v; }
+    if (trace) trace[(size_t)c * P + i] = v;
+  } else if (i < P) {
+    const int j = c * K + (i - DK);
+    T v = b[j];
+    if (take) { v = bn[j]; b[j] = v; }
+    if (trace) trace[(size_t)c * P + i] = v;
+  }
+}
+
+template <typename T>
+int mh_run_t(hmcx_ctx* ctx, const hmcx_mh_args* s) {
+  const int B = s->B, D = s->D, K = s->K, C = s->C, N = C * K, DK = D * K, P = DK + K;
+  const bool logistic = s->model == HMCX_MODEL_LOGISTIC;
+  const int link = logistic ? LINK_SIGMOID : LINK_SOFTMAX;
+  const Tiling t = make_tiling(B, D, K, C);
+  const int fpb = std::max(1, MH_EPB / K), nPB = (D + fpb - 1) / fpb;
+  const size_t nsc = (size_t)s->n_steps * C;
+  const bool buffer = s->noise_mode == HMCX_NOISE_BUFFER;
+  Workspace ws(ctx);
+  T *Wn, *bn;
+  double *sqp, *ll0p, *ll1p;
+  MhState* st;
+  // the per-(step, chain) schedule goes to the device in one copy
+  const void* hsrc[4] = {s->mult, s->site, s->u_accept, buffer ? s->noise_off : nullptr};
+  const size_t hbytes[4] = {2 * nsc * sizeof(double), 2 * nsc * sizeof(int32_t), nsc * sizeof(double),
+                            buffer ? nsc * sizeof(int64_t) : 0};
+  char *sched, *dp[4];
+  do {
+    ws.reset();
+    Wn = ws.take<T>((size_t)D * N); bn = ws.take<T>(N);
+    sqp = ws.take<double>((size_t)(nPB + 1) * C);
+    ll0p = ws.take<double>((size_t)t.nRB * C); ll1p = ws.take<double>((size_t)t.nRB * C);
+    st = ws.take<MhState>(C);
+    sched = ws.take<char>(packed_bytes(4, hbytes));
+  } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  begin_call(ctx);
+  int rc = upload_packed(ctx, sched, 4, hsrc, hbytes, dp);
+  if (rc) return rc;
+  const double* d_mult = reinterpret_cast<const double*>(dp[0]);
+  const int32_t* d_site = reinterpret_cast<const int32_t*>(dp[1]);
+  const double* d_u = reinterpret_cast<const double*>(dp[2]);
+  const int64_t* d_noff = reinterpret_cast<const int64_t*>(dp[3]);   // read in BUFFER mode only
+  if ((rc = timing_begin(ctx, ctx->stream))) return rc;
+  GraphScope gs(ctx);
+  hipStream_t st_ = ctx->stream;
+  T* W = (T*)s->W;
+  T* b = (T*)s->b;
+  {   // log-likelihood of the call's starting states (step 0's E)
+    FwdArgs<T> f = fwd_args<T>(s->X, s->Y, W, b, B, D, K, C, t, FWD_LL);
+    f.link = link;
+    f.ll_part = ll0p;
+    HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
+  }
+  for (int i = 0; i < s->n_steps; ++i) {
+    MhProposeArgs<T> pa{};
+    pa.D = D; pa.K = K; pa.C = C; pa.N = N; pa.P = P; pa.nPB = nPB; pa.fpb = fpb; pa.logistic = logistic;
+    pa.prev_acc = i > 0 ? s->out_accepted + (size_t)(i - 1) * C : nullptr;
+    pa.mult = d_mult + (size_t)i * C * 2; pa.site = d_site + (size_t)i * C * 2;
+    pa.noise_mode = s->noise_mode; pa.noise = s->noise; pa.noff = d_noff + (size_t)i * C;
+    pa.seed = s->seed; pa.chain0 = s->chain0; pa.step = s->step_base + (uint32_t)i;
+    pa.W = W; pa.b = b; pa.Wn = Wn; pa.bn = bn;
+    pa.trace = (s->out_trace && i > 0) ? (T*)s->out_trace + (size_t)(i - 1) * C * P : nullptr;
+    pa.sq_part = sqp;
+    hipLaunchKernelGGL(k_mh_propose<T>, dim3(nPB, C), dim3(256), 0, st_, pa);
+    HMCX_HIP(ctx, hipGetLastError());
+    FwdArgs<T> f = fwd_args<T>(s->X, s->Y, Wn, bn, B, D, K, C, t, FWD_LL);
+    f.link = link;
+    f.ll_part = ll1p;
+    HMCX_HIP(ctx, launch_fwd<T>(f, t, st_));
+    MhAcceptArgs<T> aa{};
+    aa.D = D; aa.K = K; aa.C = C; aa.N = N; aa.nRB = t.nRB; aa.nPB = nPB; aa.first = i == 0; aa.logistic = logistic;
+    aa.u = d_u + (size_t)i * C;
+    aa.log_prior = s->log_prior; aa.lpc0 = s->lp_const[0]; aa.lpc1 = s->lp_const[1]; aa.half_alpha = 0.5 * s->alpha;
+    aa.ll0_part = ll0p; aa.ll1_part = ll1p; aa.sq_part = sqp;
+    aa.W = W; aa.b = b;
+    aa.st = st;
+    aa.out_A = s->out_A + (size_t)i * C; aa.out_acc = s->out_accepted + (size_t)i * C;
+    aa.out_logp = s->out_logp + (size_t)i * C;
+    aa.out_E = s->out_E ? s->out_E + (size_t)i * C * 2 : nullptr;
+    hipLaunchKernelGGL(k_mh_accept<T>, dim3(C), dim3(256), 0, st_, aa);
+    HMCX_HIP(ctx, hipGetLastError());
+  }
+  {
+    const int last = s->n_steps - 1;
+    T* tr = s->out_trace ? (T*)s->out_trace + (size_t)last * C * P : nullptr;
+    hipLaunchKernelGGL(k_mh_commit<T>, dim3((unsigned)((P + 255) / 256), C), dim3(256), 0, st_, D, K, N,
+                       s->out_accepted + (size_t)last * C, Wn, bn, W, b, tr);
+    HMCX_HIP(ctx, hipGetLastError());
+  }
+  if ((rc = gs.finish())) return rc;
+  return timing_end(ctx, ctx->stream);
+}
+
 // k_sghmc_init for the chain-batched path: same arithmetic, but the working copy Wwork and the
 // momentum pW are chain-major [C][D][K] (each chain's block contiguous, so every tile of the batched
 // kernels owns whole cache lines); W stays in the caller's [D][C·K] layout.  One workgroup per
@@ -1768,6 +2015,8 @@ template int sgd_run_t<float>(hmcx_ctx*, const hmcx_sgd_args*);
 template int sgd_run_t<double>(hmcx_ctx*, const hmcx_sgd_args*);
 template int hmc_chains_run_t<float>(hmcx_ctx*, const hmcx_hmc_chains_args*);
 template int hmc_chains_run_t<double>(hmcx_ctx*, const hmcx_hmc_chains_args*);
+template int mh_run_t<float>(hmcx_ctx*, const hmcx_mh_args*);
+template int mh_run_t<double>(hmcx_ctx*, const hmcx_mh_args*);
 template int axpy_t<float>(hmcx_ctx*, int, int64_t, double, const void*, void*);
 template int axpy_t<double>(hmcx_ctx*, int, int64_t, double, const void*, void*);
 template int sumsq_t<float>(hmcx_ctx*, const void*, int64_t, double*);

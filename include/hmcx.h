@@ -11,8 +11,9 @@
  *  - C independent chains are stored chain-interleaved so the two gradient GEMMs see one
  *    [rows x C*K] matrix: weights W[D][C][K], bias b[C][K]  (C = 1 is exactly the
  *    reference's {'weights': [D,K], 'bias': [K]} layout).  The SGHMC / SGLD samplers
- *    (hmcx_sampler_args) and the multi-chain full-batch HMC (hmcx_hmc_chains_args, the
- *    reference's hmc_multicore) use it; per-(step, chain) schedules and outputs are indexed
+ *    (hmcx_sampler_args), the multi-chain full-batch HMC (hmcx_hmc_chains_args, the
+ *    reference's hmc_multicore) and the random-walk Metropolis sampler (hmcx_mh_args, the
+ *    reference's metropolis.py) use it; per-(step, chain) schedules and outputs are indexed
  *    s*C + c, Philox streams by chain id chain0 + c.
  *  - dtype: HMCX_F64 (the reference's float64) or HMCX_F32.
  *  - Return 0 on success or a negative hmcx_status; hmcx_last_error() has the message.
@@ -367,6 +368,77 @@ typedef struct hmcx_hmc_chains_args {
   void* out_mom;           /* device [n_steps][C][D*K+K] (dtype) or NULL: momentum drawn*/
 } hmcx_hmc_chains_args;
 int hmcx_hmc_chains_run(hmcx_ctx* ctx, const hmcx_hmc_chains_args* a);
+
+/* ------------------------------------------------------------------ random-walk Metropolis, linear models
+ * Replaces cpu/metropolis.py:27-64 (step / accept / random_walk) with the softmax (CPU prior) or
+ * logistic model, C chains and n_steps steps in one call.  Per step and chain, per variable v in
+ * (weights, bias):  q_new_v = q_v + (T)mult_v·z_v  (metropolis.py:59, mult = factor·scale evaluated on the
+ * host), on every coordinate when site_v = −1, else on the one flat coordinate site_v of that variable
+ * (update_sequential=False, metropolis.py:61-62).  Then E = −(ll + lp) on the sum scale (no division
+ * by N; metropolis.py:49-50 with logp = log_likelihood + log_prior), A = exp(E − E_new) and
+ *   accepted = isfinite(A) && u < A                                        (metropolis.py:42-46)
+ * — no min(1, ·): an overflowing ratio (A = inf) is REJECTED like NaN, unlike hmcx_hmc_run's accept.
+ * log prior as in hmcx_hmc_args (softmax: the constant `log_prior`; logistic: Σ_var (lp_const[var] −
+ * ½·alpha·Σθ_var²), logistic.py:15-21 order).  State in the layout of hmcx_hmc_chains_args, W [D][C*K],
+ * b [C*K], updated in place; schedules per (step, chain), index s*C + c, two entries (weights, bias)
+ * where marked [·2].  Noise: BUFFER — P = D·K + K normals per (step, chain) at noise_off[s*C + c]
+ * (weights row-major, then bias; with site ≥ 0 only the element at `site` is read); PHILOX — element i
+ * is Philox(seed, chain0 + c, step_base + s, slot 0, i), the momentum stream of hmcx_hmc_chains_run.
+ * A step is three launches: k_mh_propose (commit of the previous step, its trace row, the new proposal
+ * and its Σθ² partials in one elementwise pass), k_fwd in log-likelihood mode over all chains, and
+ * k_mh_accept; the kept state's log-likelihood is carried on the device, never evaluated twice. */
+typedef struct hmcx_mh_args {
+  int dtype;
+  int model;               /* HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC                  */
+  int B, D, K, C, n_steps; /* B = N (full batch); C chains                              */
+  double alpha;
+  double log_prior;        /* softmax: constant log prior                               */
+  double lp_const[2];      /* logistic: dim·½·log(alpha/2π) of weights, bias            */
+  const void* X;
+  const void* Y;
+  const double* mult;      /* host [n_steps*C*2]  factor·scale of (weights, bias)       */
+  const int32_t* site;     /* host [n_steps*C*2]  −1: all coordinates, else flat index  */
+  const double* u_accept;  /* host [n_steps*C]                                          */
+  int noise_mode;
+  const double* noise;     /* device, BUFFER                                            */
+  const int64_t* noise_off;/* host [n_steps*C], BUFFER                                  */
+  uint64_t seed;
+  uint32_t chain0, step_base;
+  void* W;                 /* device [D][C*K] state, updated in place                   */
+  void* b;                 /* device [C*K]                                              */
+  double* out_A;           /* device [n_steps*C]: the raw ratio (may be inf / NaN)      */
+  int32_t* out_accepted;   /* device [n_steps*C]                                        */
+  double* out_logp;        /* device [n_steps*C]: ll + lp of the state kept after step s */
+  double* out_E;           /* device [n_steps*C*2] (E_current, E_new) or NULL           */
+  void* out_trace;         /* device [n_steps][C][D*K+K] (dtype) or NULL: state after s */
+} hmcx_mh_args;
+int hmcx_mh_run(hmcx_ctx* ctx, const hmcx_mh_args* a);
+
+/* The same for the MVN model (mvn_gaussian.py:22-31): x [C][dim] state, one variable, E = nlp(x) with
+ * mu / prec / nlp_const as in hmcx_hmc_mvn_args; mult, site [n_steps*C]; BUFFER noise: dim normals per
+ * (step, chain).  One thread per chain, the whole phase in one launch.  out_logp = −nlp of the state
+ * kept after step s. */
+typedef struct hmcx_mh_mvn_args {
+  int dim, C, n_steps;
+  const double* mu;        /* device [dim] */
+  const double* prec;      /* device [dim][dim] */
+  double nlp_const;
+  const double* mult;      /* host [n_steps*C] */
+  const int32_t* site;     /* host [n_steps*C] */
+  const double* u_accept;  /* host [n_steps*C] */
+  int noise_mode;
+  const double* noise;
+  const int64_t* noise_off;
+  uint64_t seed;
+  uint32_t chain0, step_base;
+  double* x;               /* device [C][dim] */
+  double* out_A;
+  int32_t* out_accepted;
+  double* out_logp;
+  double* out_E;           /* device [n_steps*C*2] (E_current, E_new) or NULL */
+  double* out_trace;       /* device [n_steps][C][dim] or NULL */
+} hmcx_mh_mvn_args;
+int hmcx_mh_mvn_run(hmcx_ctx* ctx, const hmcx_mh_mvn_args* a);
 
 /* Leapfrog arithmetic on device vectors of n elements (dtype), for hmc.step on models without a
  * fused entry (the MLP): mode 0  y −= a·x;  mode 1  y += a·x  (hmc.py:50-53, p −= ε·g, q += ε·p).
