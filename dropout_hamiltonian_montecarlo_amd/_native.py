@@ -147,7 +147,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
-           "hmcx_allreduce_f64", "hmcx_chain_diagnostics")
+           "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query")
 
 _lib = None
 _lock = threading.Lock()
@@ -243,6 +243,9 @@ def load_library():
         if hasattr(lib, "hmcx_mh_run"):                # absent in older builds loaded for A/B runs
             lib.hmcx_mh_run.argtypes = [c_void_p, ctypes.POINTER(MhArgs)]
             lib.hmcx_mh_mvn_run.argtypes = [c_void_p, ctypes.POINTER(MhMvnArgs)]
+        if hasattr(lib, "hmcx_p2_plan_query"):         # absent in older builds loaded for A/B runs
+            lib.hmcx_p2_plan_query.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int,
+                                               ctypes.POINTER(ctypes.c_longlong)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
         lib.hmcx_mvn_eval.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                       c_void_p]

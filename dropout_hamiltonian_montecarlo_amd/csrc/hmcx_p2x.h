@@ -276,6 +276,17 @@ __device__ inline bool gather_st(__amdgpu_buffer_rsrc_t rs, int base0, int pstri
   return gather_st_u<4>(rs, base0, pstride, np, nitems, ioff, ep, abort_flag, store);
 }
 
+// wanted pairs only, to a destination of the caller's choice
+template <typename Off, typename Want, typename Store>
+__device__ inline bool gather_ws(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
+                                 Want want, unsigned ep, int* abort_flag, Store store) {
+  const int u = (np * nitems + QTH - 1) / QTH;
+  if (u <= 1) return gather_wst_u<1>(rs, base0, pstride, np, nitems, ioff, want, ep, abort_flag, store);
+  if (u == 2) return gather_wst_u<2>(rs, base0, pstride, np, nitems, ioff, want, ep, abort_flag, store);
+  if (u == 3) return gather_wst_u<3>(rs, base0, pstride, np, nitems, ioff, want, ep, abort_flag, store);
+  return gather_wst_u<4>(rs, base0, pstride, np, nitems, ioff, want, ep, abort_flag, store);
+}
+
 template <typename Off, typename Want>
 __device__ inline bool gather(__amdgpu_buffer_rsrc_t rs, int base0, int pstride, int np, int nitems, Off ioff,
                               Want want, unsigned ep, int* abort_flag, double* stage) {

@@ -12,6 +12,15 @@ struct PersistPlan2 {
   double cost;
 };
 PersistPlan2 plan_p2(int B, int D, int K, size_t tsize, int num_cus, size_t lds_max);
+// Helper workgroups (HMCX_P2_HELP): the mode a launch of plan p runs in when `want` is asked for — `want`
+// when 2·G workgroups fit the device at ONE per CU, else 0 (today's kernel path) — and the dynamic LDS of
+// that launch: more than half of a CU's, so that a chain workgroup never shares a CU with a helper.
+int p2_help_mode(const PersistPlan2& p, int K, int num_cus, size_t lds_max, int want, size_t* lds);
+// Granule arena of one launch: offset and size of every region, in granules.
+struct P2Layout {
+  long oXA, nXA, oXD, nXD, oXB, nXB, oXW, nXW, oXS, nXS, oXC, nXC, oXAh, nXAh, oXQ, nXQ, oXP, nXP, ngran;
+};
+P2Layout p2_layout(const PersistPlan2& p, int K, int pad, int help);
 template <typename T> int sghmc_p2_t(hmcx_ctx*, const hmcx_sampler_args*, const PersistPlan2&);
 
 }  // namespace hmcx

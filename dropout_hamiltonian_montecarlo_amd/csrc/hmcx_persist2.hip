@@ -19,6 +19,10 @@
 //      B-AG  drifted weights of phi                    → every member has W[F_f] for the next X·W.
 //    Per step one more all-gather (kinetic and log-likelihood partials) decides the MH accept in
 //    every workgroup identically.
+//  * When the device has room (2·G workgroups at one per CU; HMCX_P2_HELP, default on) the same launch
+//    carries G helper workgroups: helper G + b computes the step-start log-likelihood (E_current) of
+//    chain workgroup b's rows from the state the chain publishes after each accept, and draws the next
+//    step's momentum for it, so neither sits on the chain's critical path.
 //  * The two GEMMs run on MFMA (v_mfma_f64_16x16x4 / f32_16x16x4) with operands from the LDS tile;
 //    the class dimension (KC = 10 compiled in, 16 generic) pads to the 16-wide tile.  A VALU
 //    variant with the classes in registers measured 1.7x slower (LDS-latency bound).
@@ -72,8 +76,29 @@ struct Q2Args {
   //  XC (commit, one use per launch): written once per launch with the launch's last epoch; the next
   //     write is by the next launch on the same stream, which starts after every workgroup of this one,
   //     workgroup 0 and its gather included, has ended.
+  // Helper regions (help: workgroup G + b computes E_current and draws p0 for chain workgroup b).  Step s uses parity
+  // s & 1 of each; E(s) is the chain's accept epoch of step s, which a helper derives from the schedule.
+  //  ll0 slot (granule 2 of a chain workgroup's XS record, written by its helper with E(s)): every chain
+  //     workgroup polls it in accept s.  Its helper P rewrites it for step s + 2, which it starts only with
+  //     q(s+2) in hand; the chain publishes q(s+2) after its consume of accept s + 1, and no workgroup
+  //     publishes its S(s + 1) partials before its consume of S(s).
+  //  XQ (state q(s), feature team of chain → same team of helpers, epoch E(s − 1)): chain member P rewrites
+  //     its block for q(s+2) after its consume of accept s + 1, which polled the ll0(s + 1) of EVERY helper;
+  //     helper C publishes that only after its consume of XQ(s + 1), later than its consume of XQ(s).
+  //  XAh (the helpers' A-RS, row team of helpers, epoch E(s)): helper P reaches step s + 2 only with
+  //     q(s+2), published after an accept s + 1 that polled the ll0(s + 1) of every helper C — published
+  //     after C's A-RS consume of step s + 1, later than that of step s.
+  //  XP (momentum p0(s) of the slice, feature team of helpers → same team of chain, epoch
+  //     E(s − 1); E(−1) is the launch's first epoch): helper P rewrites its block for p0(s + 2) after its
+  //     ll0(s + 1), for which it consumed XQ(s + 1) from EVERY chain member C of its feature team; C
+  //     publishes q(s+1) at the end of step s, after it consumed p0(s) at the start of step s.
+  // So no chain workgroup passes accept s without every helper's ll0(s), no helper starts step s + 1
+  // without the post-accept publish of q(s+1), and the skew between the two halves is at most one step.
   int oXA, oXD, oXB, oXW, oXS;
   int oXC;                                  // commit round: one granule per workgroup
+  int oXAh, oXQ, oXP;
+  int help;                                 // 2: helper workgroups G … 2G − 1 compute E_current and draw the
+                                            // step's momentum (HMCX_P2_HELP); 0: none
   int arena_bytes;
   int pad;                                  // line-aligned producer blocks (HMCX_P2_PAD, default on)
   unsigned ep0;                             // first round epoch of this launch (unique in the arena's life)
@@ -127,6 +152,10 @@ struct P2Verdict {
   }
 };
 constexpr int P2TR_IT = 16;                 // traced leapfrog iterations
+// HMCX_P2_HELP when the environment does not set it, and the mode folded into the config-2 instantiation
+#ifndef HMCX_P2_HELP_DEFAULT
+#define HMCX_P2_HELP_DEFAULT 2
+#endif
 
 // Segment profiler (workgroup 0, thread 0): s_memtime deltas accumulate in LDS (a global
 // read-modify-write per stamp would add a memory round trip to the critical path); flushed once.
@@ -271,12 +300,17 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   const int spread = SP ? 2 : a.spread, pad = SP ? 1 : a.pad, xmap = SP ? 0 : a.xmap, fl2 = SP ? 1 : a.fl2,
             al2 = SP ? 0 : a.al2, prefetch = SP ? 1 : a.prefetch, acc1 = SP ? 1 : a.acc1,
             zoffa = SP ? 1 : a.zoff, bara = SP ? 1 : a.bar;
+  // E_current and the step's momentum p0 come from helper workgroups
+  const bool hp = (SP ? HMCX_P2_HELP_DEFAULT : a.help) != 0;
   extern __shared__ __align__(16) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15;
   const int Gr = SP ? 8 : a.Gr, Gf = SP ? 16 : a.Gf, G = Gr * Gf;
   // workgroups are dealt to the 8 XCDs round-robin by blockIdx: with the identity map feature team
   // f (blocks f, f+Gf, …) shares an XCD when Gf % 8 == 0; xmap = 1 puts each row team on one XCD
-  const int pbid = blockIdx.x;
+  // helper G + b is the twin of chain workgroup b: same (r, f) and tile, and the same XCD whenever a team
+  // region is kept in an XCD's L2 (fl2 / al2 need G % 8 == 0, so blockIdx % 8 is equal)
+  const bool helper = hp && (int)blockIdx.x >= G;
+  const int pbid = helper ? (int)blockIdx.x - G : (int)blockIdx.x;
   const int bid = xmap ? (pbid & 7) * (G >> 3) + (pbid >> 3) : pbid;
   const int r = bid / Gf, f = bid - (bid / Gf) * Gf;
   const int Br = SP ? 64 : a.Br, Bf = SP ? 49 : a.Bf, BfP = SP ? 64 : a.BfP, BFP = SP ? 65 : a.BFP, Ro = SP ? 4 : a.Ro,
@@ -362,13 +396,15 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
 
   // segment profiler: compiled out of the config-2 instantiation (SPEC = 1); SPEC = 3 is that
   // instantiation with it (HMCX_PERSIST_PROF=1 at the config-2 shape)
-  P2Prof prof{((!SP || SPEC == 3) && bid == 0 && tid == 0) ? a.prof : nullptr, profacc, 0ull, 0};
+  P2Prof prof{((!SP || SPEC == 3) && bid == 0 && tid == 0 && !helper) ? a.prof : nullptr, profacc, 0ull, 0};
   // round trace: slot 2·round = payload published, 2·round + 1 = consumed (rounds A, D, B, W)
-  unsigned long long* trb = (!SP && a.trace) ? a.trace + (size_t)bid * P2TR_IT * 8 : nullptr;
+  unsigned long long* trb = (!SP && a.trace && !helper) ? a.trace + (size_t)bid * P2TR_IT * 8 : nullptr;
   auto tstamp = [&](int s_, int it_, int slot) {
     if (trb && tid == 0 && s_ == 0 && it_ >= 0 && it_ < P2TR_IT) trb[it_ * 8 + slot] = __builtin_amdgcn_s_memrealtime();
   };
-  unsigned ep = a.ep0 - 1;                            // round epoch (same sequence in every workgroup)
+  // round epoch (same sequence in every workgroup); with helpers the launch's first epoch is E(-1), the
+  // "accept epoch" before step 0
+  unsigned ep = a.ep0 - 1 + (hp ? 1u : 0u);
   unsigned uA = 0, uD = 0, uB = 0, uW = 0, uS = 0;    // per-region use counters (buffer parity)
 
   // ---- phase A: partial logits X[R_r,F_f]·W[F_f] → XA(par, r, f) [nrow][KC], then A-RS consume:
@@ -376,10 +412,11 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   // Two A rounds may be in flight (the step-start round of E_current and iteration 0's): each is
   // published into region parity `par` with its own epoch (epA[par]), and consumed from the same.
   unsigned epA[2] = {0u, 0u};
+  const int oXA = helper ? a.oXAh : a.oXA;            // the helpers' A-RS rounds have a region of their own
   auto roundA = [&](int par) -> bool {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     epA[par] = ++ep;
-    const int reg = a.oXA + ((par * Gr + r) * Gf + f) * Br * KC;
+    const int reg = oXA + ((par * Gr + r) * Gf + f) * Br * KC;
     // zero-padded tail skipped; config 2: 49 features in every feature team → 13 k-steps (a constant:
     // the k loop unrolls completely)
     const int nkp = SP ? 13 : WPA == 1 ? (nfeat + 3) / 4 : (BfP / 4) / WPA;
@@ -411,7 +448,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   };
   auto consumeA = [&](int par) -> bool {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
-    const int base0 = a.oXA + (par * Gr + r) * Gf * Br * KC;
+    const int base0 = oXA + (par * Gr + r) * Gf * Br * KC;
     const unsigned ep = epA[par];
     ++uA;
     if (spread & 1) {
@@ -434,6 +471,155 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     return all_ok(ok, ish);
   };
 
+  // ---- helpers on: the slice's momentum p0(s) arrives from the helpers (XP).  Item j < nfeat·KC is class
+  //      j % KC of slice feature j / KC (from the member that owns it), then KC bias items from member 0;
+  //      two items per thread and chunk.  The loads of a step's first chunk are issued before the previous
+  //      accept poll (p0 does not depend on the accept) and tested at the step start.
+  const int nXPi = nfeat * KC + KC;
+  gran_t xpv[2];
+  int xpo[2];
+  const auto xp_issue = [&](int s_, int c) {
+    const int tid = opaque((int)threadIdx.x);
+    const int perQ = p2_pad(Fo * KC + KC, pad);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      int j = c * 2 * QTH + u * QTH + tid;
+      if (j >= nXPi) j = nXPi - 1;                    // nothing wanted: an alias that matches with the rest
+      int p = 0, i = Fo * KC + j - nfeat * KC;
+      if (j < nfeat * KC) {
+        const int d = j / KC;
+        p = d / Fo;
+        i = (d - p * Fo) * KC + (j - d * KC);
+      }
+      xpo[u] = (a.oXP + (((s_ & 1) * Gf + f) * Gr + p) * perQ + i) * 16;
+      xpv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, xpo[u], 0, 16 /* sc1 */);
+    }
+  };
+  // tests the chunk (re-reading it until it is complete) and stores it: pWs, and pbsh / pb0sh for the bias
+  const auto xp_finish = [&](int c, unsigned e) -> bool {
+    const int tid = opaque((int)threadIdx.x);
+    unsigned long long t0 = 0;
+    for (int spins = 0;; ++spins) {
+      if (pass_complete(gran_miss(xpv[0], e) | gran_miss(xpv[1], e))) break;
+      if (p2_pass_missed(spins, t0, a.abort_flag, a.oXP, e)) return false;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) xpv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, xpo[u], 0, 16 /* sc1 */);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = c * 2 * QTH + u * QTH + tid;
+      if (j >= nXPi) continue;
+      const T v = (T)decode(xpv[u]);
+      if (j < nfeat * KC) {
+        pWs[(j / KC) * 16 + (j - (j / KC) * KC)] = v;
+      } else {
+        pbsh[j - nfeat * KC] = v;
+        pb0sh[j - nfeat * KC] = v;
+      }
+    }
+    return true;
+  };
+
+  // ---- helper workgroups (help): E_current of every step, off the chain's workgroups.  ll0 = ll(q_s;
+  //      batch s) is first used in the accept at the END of step s, so the helper of (r, f) computes it
+  //      while the chain runs the step's leapfrogs: the same A-gemm, A-RS exchange (region XAh), log-softmax
+  //      and row order as the chain's own it = -1 round, from the state the chain's feature team published
+  //      after the previous accept (XQ), into slot 2 of its twin's accept record.  Helpers store nothing to
+  //      W or b and take no part in the commit round; they leave after the last step's publish, or from a
+  //      poll that timed out or saw the abort word (the chain then sees the word in its accept poll).
+  if (helper) {
+    const int perQ = p2_pad(Fo * KC + KC, pad);
+    unsigned eacc = a.ep0;                            // E(s - 1): the chain's accept epoch of the previous step
+    // p0(sn) of the team's slice, 1/Gr per member (its owned features; member 0 the bias too), drawn as
+    // the chain draws its owned elements
+    const auto pubP = [&](int sn, unsigned e) {
+      const int tid = opaque((int)threadIdx.x);
+      const int reg = a.oXP + ((((sn & 1) * Gf + f) * Gr + r) * perQ);
+      if (tid < Fo * KC) {
+        put_t(fl2, rs, reg + tid, own ? (double)noise1<T>(a, sn, 0u, (uint32_t)e_own) : 0.0, e);
+      } else if (r == 0 && tid < Fo * KC + KC) {
+        const int k = tid - Fo * KC;
+        put_t(fl2, rs, reg + tid, k < K ? (double)noise1<T>(a, sn, 0u, (uint32_t)(D * K + k)) : 0.0, e);
+      }
+    };
+    pubP(0, eacc);
+    for (int s = 0; s < a.n_steps; ++s) {
+      const int tid = opaque((int)threadIdx.x), lane = tid & 63;
+      const int n = sched_at(inl, s, a.inl[sched_k(s)].n_iter, a.n_iter);
+      if (s == 0) {
+        const int64_t rw = sched_at(inl, s, a.inl[sched_k(s)].row0, a.row0);
+        load_step_rows<T>(Xs, Yo, reinterpret_cast<const T*>(a.X) + (size_t)rw * D,
+                          reinterpret_cast<const T*>(a.Y) + (size_t)rw * K, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K,
+                          Ro, nro, ro0);
+        if (tid < 16) b0sh[tid] = bsh[tid];           // q_0 came from W and b, as in the chain
+        __syncthreads();
+      } else {
+        // q_s: the owned slices of the feature team's Gr chain members (+ the bias, from member 0)
+        const int ni = Fo * KC + KC;
+        const int base0 = a.oXQ + ((s & 1) * Gf + f) * Gr * perQ;
+        // a helper idles for most of a step: until the chain's step ends, ONE thread polls ONE granule
+        // (member 0's first, always published) with long naps, so that 2·G·QTH spinning threads do not load
+        // the fabric under the chain's rounds; after a timeout or the abort word the gather below leaves
+        if (tid == 0) {
+          unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+          for (int spins = 0;; ++spins) {
+            const gran_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, base0 * 16, 0, 16 /* sc1 */);
+            if (pass_complete(gran_miss(v, eacc))) break;
+            if ((spins & 63) == 63 && p2_spin_over(t0, a.abort_flag, base0, eacc)) break;
+            __builtin_amdgcn_s_sleep(32);
+          }
+        }
+        __syncthreads();
+        const bool ok = gather_ws(rs, base0, perQ, Gr, ni, [](int i) { return i; },
+                                  [&](int p, int i) { return i < Fo * KC ? p * Fo + i / KC < nfeat : p == 0; }, eacc,
+                                  a.abort_flag, [&](int q, double v) {
+          const int p = q / ni, i = q - p * ni;
+          if (i < Fo * KC) Wf[(p * Fo + i / KC) * 16 + i % KC] = (T)v;
+          else b0sh[i - Fo * KC] = (T)v;
+        });
+        if (!all_ok(ok, ish)) return;
+      }
+      // the chain's epochs of step s: 3 rounds per leapfrog with the B all-reduce, 4 (none after the last
+      // B-RS) without, then the accept round; the chain runs no it = -1 round when helpers do
+      eacc += (n > 0 ? (bar ? 3u * (unsigned)n : 4u * (unsigned)n - 1u) : 0u) + 1u;
+      ep = eacc - 1;
+      const int par = s & 1;
+      roundA(par);                                    // epoch E(s)
+      if (!consumeA(par)) return;
+      {
+        const int k = lane & 15, grp = tid >> 4;
+        const bool kv = k < K;
+        for (int ii = grp; ii < nro; ii += QTH / 16) {
+          const T z = kv ? clipz(Zo[ii * 16 + k] + b0sh[k], hi, lo) : (T)-__builtin_inf();
+          const T m = g16_max2(z);
+          const T e = kv ? exp(z - m) : T(0);
+          const T sm = g16_sum2(e);
+          const T lse = log(sm) + m;                                          // softmax.py:18
+          const double t = kv ? (double)(Yo[ii * 16 + k] * (z - lse)) : 0.0;  // softmax.py:19-20
+          const double rsum = g16_sum2(t);
+          if (k == 0) rowll[ii] = rsum;
+        }
+        __syncthreads();
+        if (tid == 0) {
+          double v = 0.0;
+          for (int ii = 0; ii < nro; ++ii) v += rowll[ii];
+          put(rs, a.oXS + ((s & 1) * G + bid) * NXS + 2, v, eacc);
+        }
+      }
+      if (s + 1 < a.n_steps) pubP(s + 1, eacc);
+      // the next step's tile and labels: Xs and Yo have no reader left behind the barrier above, and the
+      // next reader comes after the barrier that ends the XQ gather
+      if (s + 1 < a.n_steps) {
+        const int64_t rn = sched_at(inl, s + 1, a.inl[sched_k(s + 1)].row0, a.row0);
+        load_step_rows<T>(Xs, Yo, reinterpret_cast<const T*>(a.X) + (size_t)rn * D,
+                          reinterpret_cast<const T*>(a.Y) + (size_t)rn * K, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K,
+                          Ro, nro, ro0);
+      }
+    }
+    verdict.done = true;                              // nothing to report: the chain workgroups decide
+    return;
+  }
+
   for (int s = 0; s < a.n_steps; ++s) {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     const double epsd = sched_at(inl, s, a.inl[sched_k(s)].eps, a.eps);
@@ -452,17 +638,35 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     //      previous accept round travelled), momentum (hmc.py:82-87), step-start copies
     if (s == 0 || !prefetch) load_step_rows<T>(Xs, Yo, Xg, Yg, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K, Ro, nro, ro0);
     for (int e = tid; e < BfP * 16; e += QTH) Wf0[e] = Wf[e];
-    // momentum (hmc.py:82-87): the owned elements' by their threads, the bias's by the last 16 threads
-    // (not the owners of elements 0..15: one Box–Muller latency per thread, not two)
-    pw = own ? noise1<T>(a, s, 0u, (uint32_t)e_own) : T(0);
+    if (hp) {
+      // momentum (hmc.py:82-87) from the helpers: the whole slice's p0 into pWs, the bias's into pbsh / pb0sh; then the owned
+      // element from pWs and iteration 0's drift of the slice (sghmc.py:32) — behind the barrier that
+      // ends the chunk, so the step-start copy above has read Wf
+      if (tid >= QTH - 16) b0sh[tid - (QTH - 16)] = bsh[tid - (QTH - 16)];
+      if (s == 0) xp_issue(0, 0);
+      for (int c = 0; c * 2 * QTH < nXPi; ++c) {
+        if (c > 0) xp_issue(s, c);
+        if (!all_ok(xp_finish(c, ep), ish)) return;
+      }
+      pw = own ? pWs[wl] : T(0);
+      if (n > 0)
+        for (int j = tid; j < nfeat * KC; j += QTH) {
+          const int l = (j / KC) * 16 + (j - (j / KC) * KC);
+          Wf[l] = Wf[l] + eps * pWs[l];
+        }
+    } else {
+      // momentum (hmc.py:82-87): the owned elements' by their threads, the bias's by the last 16 threads
+      // (not the owners of elements 0..15: one Box–Muller latency per thread, not two)
+      pw = own ? noise1<T>(a, s, 0u, (uint32_t)e_own) : T(0);
+      if (tid >= QTH - 16) {
+        const int k = tid - (QTH - 16);
+        pbsh[k] = k < K ? noise1<T>(a, s, 0u, (uint32_t)(D * K + k)) : T(0);
+        pb0sh[k] = pbsh[k];
+        b0sh[k] = bsh[k];
+      }
+    }
     const T pw0 = pw;
     w0 = wv;
-    if (tid >= QTH - 16) {
-      const int k = tid - (QTH - 16);
-      pbsh[k] = k < K ? noise1<T>(a, s, 0u, (uint32_t)(D * K + k)) : T(0);
-      pb0sh[k] = pbsh[k];
-      b0sh[k] = bsh[k];
-    }
     const double kin0 = wsum((double)pw * (double)pw, dsh);
     double kb0 = 0.0;
     for (int k = 0; k < K; ++k) kb0 += (double)pbsh[k] * (double)pbsh[k];
@@ -470,11 +674,12 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     // ---- it = -1: log-likelihood of my rows at the step-start state (E_current).  (Round 5 measured
     //      issuing iteration 0's A round before consuming this one, both rounds in flight: 1.724 vs
     //      1.701 ms per driver-shape launch, 3 A/B pairs — slower, not kept.)
+    //      With helpers (hp) the round is theirs, and the drift was done above.
     double ll0 = 0.0, ll_last = 0.0;
-    prof.stamp(11);
+    if (!hp) prof.stamp(11);
     const int parm1 = (int)(uA & 1);
-    roundA(parm1);
-    if (n > 0) {
+    if (!hp) roundA(parm1);
+    if (n > 0 && !hp) {
       // iteration 0's drift of the whole F_f slice by p0 (every member computes it identically;
       // sghmc.py:32), by the waves that do not poll this A-RS round, while the partials travel —
       // after a barrier: every wave's A-gemm has read Wf
@@ -495,8 +700,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
         }
       }
     }
-    if (!consumeA(parm1)) return;
-    {
+    if (!hp) {
+      if (!consumeA(parm1)) return;
       const int k = lane & 15, grp = tid >> 4;
       const bool kv = k < K;
       for (int ii = grp; ii < nro; ii += QTH / 16) {
@@ -825,8 +1030,9 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       const int reg = a.oXS + ((int)(uS & 1) * G + bid) * NXS;
       if (tid == 0) put(rs, reg + 0, kin0, ep);
       if (tid == 1) put(rs, reg + 1, kin1w, ep);
-      if (tid == 2) put(rs, reg + 2, ll0, ep);
+      if (tid == 2 && !hp) put(rs, reg + 2, ll0, ep);   // hp: this workgroup's helper wrote it
     }
+    if (hp && s + 1 < a.n_steps) xp_issue(s + 1, 0);   // p0 of the next step: tested at its start
     // next step's tile and labels while the partials travel: Xs and Yo have no reader left in this
     // step (the last B-gemm and softmax ended before a barrier)
     // (measured: loading it with only the half of the workgroup that does not poll the accept round
@@ -892,6 +1098,13 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       if (a.out_E) { a.out_E[2 * s] = Ecur; a.out_E[2 * s + 1] = Enew; }
     }
     __syncthreads();
+    // q_{s+1} for the helpers of this feature team: the owned slice (the bias too from member 0), one
+    // store per thread, with the accept's epoch
+    if (hp && s + 1 < a.n_steps) {
+      const int reg = a.oXQ + ((((s + 1) & 1) * Gf + f) * Gr + r) * p2_pad(Fo * KC + KC, pad);
+      if (tid < Fo * KC) put_t(fl2, rs, reg + tid, own ? (double)wv : 0.0, ep);
+      else if (r == 0 && tid < Fo * KC + KC) put_t(fl2, rs, reg + tid, (double)bsh[tid - Fo * KC], ep);
+    }
   }
   prof.stamp(0);
   prof.flush();
@@ -983,17 +1196,57 @@ PersistPlan2 plan_p2(int B, int D, int K, size_t ts, int num_cus, size_t lds_max
   return best;
 }
 
+int p2_help_mode(const PersistPlan2& p, int K, int num_cus, size_t lds_max, int want, size_t* lds) {
+  const int G = p.Gr * p.Gf, KC = kc_of(K);
+  const size_t half = lds_max / 2 + 1024;        // two such workgroups do not fit one CU
+  const size_t need = std::max(p.lds, half);
+  // the helpers gather q_s with at most 4 granules per thread (gather_ws)
+  const bool ok = want == 2 && 2L * G <= num_cus && need <= lds_max && p.Gr * (p.Fo * KC + KC) <= 4 * QTH;
+  if (lds) *lds = ok ? need : p.lds;
+  return ok ? 2 : 0;
+}
+
+P2Layout p2_layout(const PersistPlan2& p, int K, int pad, int help) {
+  const long G = (long)p.Gr * p.Gf;
+  const int KC = kc_of(K);
+  P2Layout l{};
+  // XA, XD, XB, XW, XS (double-buffered), the commit round ('done' granules + the launch's decision word,
+  // one spare granule), then the helpers' regions (empty without helpers)
+  l.nXA = 2 * G * p.Br * KC;
+  l.nXD = 2 * G * p2_pad(KC + 1 + p.Ro * KC, pad);
+  l.nXB = 2 * G * p2_pad(KC + 1 + p.Bf * KC, pad);
+  l.nXW = 2 * G * p2_pad(p.Fo * KC, pad);
+  l.nXS = 2 * G * (pad ? 8 : 4);
+  l.nXC = G + 2;
+  l.nXAh = help ? l.nXA : 0;
+  l.nXQ = help ? 2 * G * p2_pad(p.Fo * KC + KC, pad) : 0;
+  l.oXA = 0;
+  l.oXD = l.oXA + l.nXA;
+  l.oXB = l.oXD + l.nXD;
+  l.oXW = l.oXB + l.nXB;
+  l.oXS = l.oXW + l.nXW;
+  l.oXC = l.oXS + l.nXS;
+  l.oXAh = l.oXC + l.nXC;
+  l.oXQ = l.oXAh + l.nXAh;
+  l.nXP = l.nXQ;
+  l.oXP = l.oXQ + l.nXQ;
+  l.ngran = l.oXP + l.nXP;
+  return l;
+}
+
 template <typename T>
 int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl) {
   const int G = pl.Gr * pl.Gf, K = s->K, KC = kc_of(K);
   const size_t n = (size_t)s->n_steps;
-  // granule arena: XA, XD, XB, XW, XS (double-buffered), then the abort word
   static const int pad = !(getenv("HMCX_P2_PAD") && getenv("HMCX_P2_PAD")[0] == '0');
-  const long nXA = 2L * G * pl.Br * KC, nXD = 2L * G * p2_pad(KC + 1 + pl.Ro * KC, pad),
-             nXB = 2L * G * p2_pad(KC + 1 + pl.Bf * KC, pad), nXW = 2L * G * p2_pad(pl.Fo * KC, pad),
-             nXS = 2L * G * (pad ? 8 : 4);
-  const long nXC = G + 1;                        // 'done' granules + the launch's decision word
-  const long ngran = nXA + nXD + nXB + nXW + nXS + nXC + 1;
+  // HMCX_P2_HELP (read per call): 0 = E_current and the momentum draw on the chain's workgroups, 2 = on G
+  // helper workgroups (1, E_current alone, measured no gain at the 20-step shape and is not built)
+  const char* help_env = getenv("HMCX_P2_HELP");
+  size_t lds = pl.lds;
+  const int help = p2_help_mode(pl, K, ctx->num_cus, ctx->lds_max, help_env ? atoi(help_env) : HMCX_P2_HELP_DEFAULT,
+                                &lds);
+  const P2Layout lay = p2_layout(pl, K, pad, help);
+  const long ngran = lay.ngran;
   if (ngran * 16 > 0x7fffffffL) return set_error(ctx, HMCX_EUNSUPPORTED, "persistent SGHMC: arena too large");
   int rc = abort_precheck(ctx);                  // an earlier launch's timeout, before enqueueing more
   if (rc) return rc;
@@ -1011,7 +1264,7 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   char* arena = ctx->gx_arena;
   unsigned rounds = 0;                           // ≤ 5 epochs per leapfrog iteration (it = -1 … L-1, accept)
   for (size_t i = 0; i < n; ++i) rounds += 5u * (unsigned)(std::max(s->n_iter[i], 0) + 2);
-  rounds += 1;                                   // the commit round
+  rounds += 1 + (help ? 1 : 0);                  // the commit round; with helpers E(-1), the launch's first epoch
   unsigned ep0 = 1;
   if ((rc = gx_epochs(ctx, rounds, &ep0))) return rc;
   Q2Args a{};
@@ -1057,17 +1310,18 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   a.seed = s->seed; a.chain0 = s->chain0; a.step_base = s->step_base;
   a.W = s->W; a.b = s->b;
   a.arena = arena;
-  a.oXA = 0; a.oXD = (int)nXA; a.oXB = (int)(nXA + nXD); a.oXW = (int)(nXA + nXD + nXB);
-  a.oXS = (int)(nXA + nXD + nXB + nXW);
-  a.oXC = (int)(nXA + nXD + nXB + nXW + nXS);
+  a.oXA = (int)lay.oXA; a.oXD = (int)lay.oXD; a.oXB = (int)lay.oXB; a.oXW = (int)lay.oXW;
+  a.oXS = (int)lay.oXS; a.oXC = (int)lay.oXC; a.oXAh = (int)lay.oXAh; a.oXQ = (int)lay.oXQ;
+  a.oXP = (int)lay.oXP;
+  a.help = help;
   a.arena_bytes = (int)(ngran * 16);
   a.ep0 = ep0;
   a.pad = pad;
   static const bool dbg = getenv("HMCX_P2_DEBUG") && getenv("HMCX_P2_DEBUG")[0] == '1';
   if (dbg)
     fprintf(stderr, "[hmcx p2] B=%d D=%d K=%d plan %dx%d Br=%d Bf=%d BfP=%d Ro=%d Fo=%d; granule bases XA %d XD %d XB %d "
-            "XW %d XS %d XC %d; epochs %u..%u\n", s->B, s->D, K, pl.Gr, pl.Gf, pl.Br, pl.Bf, pl.BfP, pl.Ro, pl.Fo,
-            a.oXA, a.oXD, a.oXB, a.oXW, a.oXS, a.oXC, ep0, ep0 + rounds - 1);
+            "XW %d XS %d XC %d; help %d XAh %d XQ %d XP %d; epochs %u..%u\n", s->B, s->D, K, pl.Gr, pl.Gf, pl.Br, pl.Bf,
+            pl.BfP, pl.Ro, pl.Fo, a.oXA, a.oXD, a.oXB, a.oXW, a.oXS, a.oXC, a.help, a.oXAh, a.oXQ, a.oXP, ep0, ep0 + rounds - 1);
   {
     const int HA = KC + 1;
     const bool fits = pl.Gf * pl.Ro * KC <= QSTAGE && pl.Gf * (HA + pl.Ro * KC) <= QSTAGE &&
@@ -1135,16 +1389,20 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   const bool spec = sizeof(T) == 8 && KC == 10 && s->B == 500 && s->D == 784 && K == 10 && pl.Gr == 8 && pl.Gf == 16 &&
                     pl.Br == 64 && pl.Bf == 49 && pl.BfP == 64 && pl.BFP == 65 && pl.Ro == 4 && pl.Fo == 7 &&
                     a.spread == 2 && a.pad == 1 && a.xmap == 0 && a.fl2 == 1 && a.al2 == 0 && a.prefetch == 1 &&
-                    a.acc1 == 1 && a.zoff == 1 && a.bar == 1 && !a.trace;
+                    a.acc1 == 1 && a.zoff == 1 && a.bar == 1 && !a.trace && a.help == HMCX_P2_HELP_DEFAULT;
   static const bool no_spec = getenv("HMCX_P2_SPEC") && getenv("HMCX_P2_SPEC")[0] == '0';
-  const void* kfn = (spec && !no_spec) ? (a.prof ? (const void*)k_sghmc_p2<T, 10, 3> : (const void*)k_sghmc_p2<T, 10, 1>)
-                    : KC == 10 ? (const void*)k_sghmc_p2<T, 10> : (const void*)k_sghmc_p2<T, 16>;
+  const void* kfn = KC == 10 ? (const void*)k_sghmc_p2<T, 10> : (const void*)k_sghmc_p2<T, 16>;
+  if constexpr (sizeof(T) == 8) {                // config 2 is f64: no folded f32 kernel is built
+    if (spec && !no_spec) kfn = a.prof ? (const void*)k_sghmc_p2<T, 10, 3> : (const void*)k_sghmc_p2<T, 10, 1>;
+  }
   void* kargs[] = {&a};
-  // co-residency of all G workgroups is checked here (occupancy query × CUs, cached per kernel); a
-  // plain launch then has the same residency as a cooperative one without its per-launch host cost
+  // co-residency of all workgroups (G, or 2·G at one per CU with helpers) is checked here (occupancy
+  // query × CUs, cached per kernel); a plain launch then has the same residency as a cooperative one
+  // without its per-launch host cost
+  const int nwg = help ? 2 * G : G;
   int per_cu = 0;
-  if ((rc = kernel_occupancy(ctx, kfn, QTH, (int)pl.lds, &per_cu))) return rc;
-  if ((long)per_cu * ctx->num_cus < G)
+  if ((rc = kernel_occupancy(ctx, kfn, QTH, (int)lds, &per_cu))) return rc;
+  if ((long)per_cu * ctx->num_cus < nwg || (help && per_cu != 1))
     return set_error(ctx, HMCX_EUNSUPPORTED, "persistent SGHMC: workgroups cannot be co-resident");
   // the verdict is sticky (P2Verdict): zeroed here, only a workgroup that leaves without committing
   // stores 1.  The call's output slot is idle at enqueue time (the caller collected its previous use).
@@ -1153,7 +1411,7 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   else if (a.verdict)
     HMCX_HIP(ctx, hipMemsetAsync(a.verdict, 0, sizeof(int), ctx->stream));
   if ((rc = timing_begin(ctx, ctx->stream))) return rc;
-  HMCX_HIP(ctx, hipLaunchKernel(kfn, dim3(G), dim3(QTH), kargs, (unsigned)pl.lds, ctx->stream));
+  HMCX_HIP(ctx, hipLaunchKernel(kfn, dim3(nwg), dim3(QTH), kargs, (unsigned)lds, ctx->stream));
   if ((rc = timing_end(ctx, ctx->stream))) return rc;
   if (s->out_host && direct_host) {
     if (!dprof && !dtrace) return HMCX_OK;
@@ -1229,6 +1487,31 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   if (flag) return set_error(ctx, HMCX_EHIP, "persistent SGHMC: hand-off timed out (workgroups not co-resident?)");
   return HMCX_OK;
 }
+
+}  // namespace hmcx
+
+// Plan, helper mode and arena layout a call of this shape would get on a device of num_cus CUs (host
+// arithmetic only; the tests of the plan read it).  out[0..10]: ok, Gr, Gf, Br, Bf, BfP, Ro, Fo, plan LDS,
+// helper mode, launch LDS; out[11]: workgroups launched; out[12..30]: P2Layout in declaration order.
+extern "C" int hmcx_p2_plan_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
+                                  long long* out) {
+  using namespace hmcx;
+  const PersistPlan2 p = plan_p2(B, D, K, (size_t)tsize, num_cus, (size_t)lds_max);
+  for (int i = 0; i < 31; ++i) out[i] = 0;
+  out[0] = p.ok;
+  if (!p.ok) return 0;
+  size_t lds = p.lds;
+  const int help = p2_help_mode(p, K, num_cus, (size_t)lds_max, want, &lds);
+  const P2Layout l = p2_layout(p, K, pad, help);
+  const long long v[] = {p.Gr, p.Gf, p.Br, p.Bf, p.BfP, p.Ro, p.Fo, (long long)p.lds, help, (long long)lds,
+                         (long long)(help ? 2 : 1) * p.Gr * p.Gf,
+                         l.oXA, l.nXA, l.oXD, l.nXD, l.oXB, l.nXB, l.oXW, l.nXW, l.oXS, l.nXS, l.oXC, l.nXC, l.oXAh, l.nXAh,
+                         l.oXQ, l.nXQ, l.oXP, l.nXP, l.ngran};
+  for (int i = 0; i < 30; ++i) out[1 + i] = v[i];
+  return 0;
+}
+
+namespace hmcx {
 
 template int sghmc_p2_t<float>(hmcx_ctx*, const hmcx_sampler_args*, const PersistPlan2&);
 template int sghmc_p2_t<double>(hmcx_ctx*, const hmcx_sampler_args*, const PersistPlan2&);

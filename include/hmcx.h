@@ -252,6 +252,17 @@ int hmcx_get_mlp_forward_counts(const hmcx_ctx* ctx, int64_t counts[3]);
 int hmcx_philox_schedule(uint64_t seed, uint32_t chain0, int C, uint32_t step_base, int n_steps,
                          double path_length, const double* eps, double* L, int32_t* n_iter, double* u);
 
+/* Launch plan of the persistent single-chain SGHMC kernel for a call of this shape on a device of
+ * num_cus CUs with lds_max bytes of LDS per CU (host arithmetic only, no device needed): tsize = 4 or 8,
+ * pad as HMCX_P2_PAD, want as HMCX_P2_HELP.  out: host long long[31] —
+ *   [0] plan found, [1..7] Gr, Gf, Br, Bf, BfP, Ro, Fo, [8] plan LDS bytes, [9] helper mode the launch
+ *   runs in (2, or 0 when want is not 2 or 2·G workgroups at one per CU do not fit), [10] dynamic LDS of
+ *   the launch,
+ *   [11] workgroups launched, [12..29] offset and size in granules of the arena regions XA, XD, XB, XW, XS,
+ *   XC, XAh, XQ, XP, [30] granules in the arena. */
+int hmcx_p2_plan_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
+                       long long* out);
+
 /* Replaces hamiltonian/inference/cpu/sgld.py:31-46 (step): p = N(0,(2ε)²) − ½ε∇U; q += p.
  * With pW/pb set: hamiltonian/inference/gpu/sgld.py:11-20, p = ν⊙p_prev − ½ε∇U with
  * ν ~ N(0,(2ε)²), q += p, p written back to pW/pb. */
