@@ -147,7 +147,8 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
-           "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query")
+           "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query", "hmcx_p2_ahead_query",
+           "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule")
 
 _lib = None
 _lock = threading.Lock()
@@ -246,6 +247,12 @@ def load_library():
         if hasattr(lib, "hmcx_p2_plan_query"):         # absent in older builds loaded for A/B runs
             lib.hmcx_p2_plan_query.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int,
                                                ctypes.POINTER(ctypes.c_longlong)]
+        if hasattr(lib, "hmcx_set_sghmc_ahead"):       # absent in older builds loaded for A/B runs
+            lib.hmcx_set_sghmc_ahead.argtypes = [c_void_p, c_int]
+            lib.hmcx_sghmc_ahead_note.argtypes = [c_void_p, c_i32p, c_int]
+            lib.hmcx_p2_ahead_rule.argtypes = [c_int, c_int, c_int]
+            lib.hmcx_p2_ahead_query.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int,
+                                                ctypes.POINTER(ctypes.c_longlong)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
         lib.hmcx_mvn_eval.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                       c_void_p]
@@ -292,6 +299,20 @@ class Context:
         """0 auto, 1 kernel-per-phase, 2 persistent (see include/hmcx.h)."""
         self.check(self.lib.hmcx_set_sghmc_path(self.h, int(path)), "hmcx_set_sghmc_path")
         self.path = int(path)
+
+    def set_sghmc_ahead(self, mode):
+        """Look-ahead of the persistent SGHMC launch: 0 off, 1 on, 2 auto (include/hmcx.h)."""
+        self.check(self.lib.hmcx_set_sghmc_ahead(self.h, int(mode)), "hmcx_set_sghmc_ahead")
+
+    def sghmc_ahead_note(self, accepted):
+        """Report a finished call's accept flags to the auto rule (include/hmcx.h hmcx_sghmc_ahead_note)."""
+        if not hasattr(self.lib, "hmcx_sghmc_ahead_note"):
+            return
+        if hasattr(accepted, "ctypes") and accepted.dtype.str == "<i4" and accepted.flags.c_contiguous:
+            self.lib.hmcx_sghmc_ahead_note(self.h, accepted.ctypes.data_as(c_i32p), int(accepted.size))
+            return
+        flags = [1 if v else 0 for v in accepted]
+        self.lib.hmcx_sghmc_ahead_note(self.h, (ctypes.c_int32 * len(flags))(*flags), len(flags))
 
     def clear_abort(self):
         """Lower the context's persistent-launch abort word (include/hmcx.h hmcx_clear_abort)."""

@@ -667,6 +667,21 @@ int hmcx_set_sghmc_path(hmcx_ctx* ctx, int path) {
   return HMCX_OK;
 }
 
+int hmcx_set_sghmc_ahead(hmcx_ctx* ctx, int mode) {
+  HMCX_GUARD_CTX(ctx);
+  if (mode < 0 || mode > 2) return set_error(ctx, HMCX_EINVAL, "mode must be 0 (off), 1 (on), 2 (auto)");
+  ctx->sghmc_ahead = mode;
+  return HMCX_OK;
+}
+
+int hmcx_sghmc_ahead_note(hmcx_ctx* ctx, const int32_t* accepted, int n) {
+  HMCX_GUARD_CTX(ctx);
+  if (n < 0 || (n > 0 && !accepted)) return set_error(ctx, HMCX_EINVAL, "ahead_note: null flags");
+  for (int i = 0; i < n; ++i) ctx->ahead_flags = (ctx->ahead_flags << 1) | (accepted[i] ? 1ull : 0ull);
+  ctx->ahead_seen = (int)std::min<long long>((long long)ctx->ahead_seen + n, 64);
+  return HMCX_OK;
+}
+
 int hmcx_set_mlp_fuse(hmcx_ctx* ctx, int on) {
   HMCX_GUARD_CTX(ctx);
   ctx->mlp_nofuse = on ? 0 : 1;

@@ -14,6 +14,12 @@ struct hmcx_ctx {
   std::string err;
   int graph_mode = 0;
   int sghmc_path = 0;          // 0 auto (persistent when eligible), 1 kernel-per-phase, 2 persistent only
+  // persistent SGHMC look-ahead (hmcx_set_sghmc_ahead): the mode asked for; under auto, the mode of the last
+  // launch and the accept flags of the last resolved steps the caller reported (bit 0 = the latest)
+  int sghmc_ahead = 2;
+  int ahead_on = 1;
+  uint64_t ahead_flags = 0;
+  int ahead_seen = 0;
   int num_cus = 256;
   size_t lds_max = 160 * 1024;
   // device workspace (grows; freed only after a stream sync)

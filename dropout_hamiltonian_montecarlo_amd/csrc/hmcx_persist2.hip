@@ -23,6 +23,10 @@
 //    carries G helper workgroups: helper G + b computes the step-start log-likelihood (E_current) of
 //    chain workgroup b's rows from the state the chain publishes after each accept, and draws the next
 //    step's momentum for it, so neither sits on the chain's critical path.
+//  * Look-ahead (HMCX_P2_AHEAD / hmcx_set_sghmc_ahead, default auto → on): instead of helpers the launch
+//    carries a SECOND chain team on those G workgroups.  Lane 0 runs the even steps, lane 1 the odd ones, each
+//    assuming that the step before it rejects (≈ 91 % do at the benchmark's settings); a step whose assumption
+//    failed is run again from the true state, so every step that counts is computed exactly as without it.
 //  * The two GEMMs run on MFMA (v_mfma_f64_16x16x4 / f32_16x16x4) with operands from the LDS tile;
 //    the class dimension (KC = 10 compiled in, 16 generic) pads to the 16-wide tile.  A VALU
 //    variant with the classes in registers measured 1.7x slower (LDS-latency bound).
@@ -94,6 +98,20 @@ struct Q2Args {
   //     publishes q(s+1) at the end of step s, after it consumed p0(s) at the start of step s.
   // So no chain workgroup passes accept s without every helper's ll0(s), no helper starts step s + 1
   // without the post-accept publish of q(s+1), and the skew between the two halves is at most one step.
+  // Look-ahead regions (ahead: lane l = blocks [l·G, (l + 1)·G) runs the steps k ≡ l mod 2; each lane has
+  // XA … XS regions and an epoch sequence of its own, for which the arguments above hold lane by lane — a
+  // redone step is one more step of the lane's sequence).  Both cross-lane records carry the tag T(k) =
+  // ep0 + k of the step, never a lane epoch, and live in the slot of parity k & 1, which is the lane.
+  //  XV (verdict V(k): "step k is final and did / did not change the state", workgroup b of lane k & 1 →
+  //     its twin b of the other lane): V(k + 2) is written when step k + 2 is final, after this workgroup
+  //     read V(k + 1); its twin publishes V(k + 1) only after it read V(k).
+  //  XQ (state q(k+1) after an accepted step k, feature team of lane k & 1 → same team of the other lane,
+  //     written before V(k)): member P rewrites its block for step k + 2 after it read V(k + 1) from its
+  //     twin, which published it after its accept round of the final run of step k + 1; that round polled
+  //     the partials of EVERY workgroup of the twin's lane, each published after its gather of XQ(k) (a
+  //     lane gathers XQ(k) before it redoes step k + 1, or, lane 0 at the end of the call, never rewrites).
+  // The oldest unresolved step waits for nothing (V(k − 1) is published before its lane goes on), so the
+  // lanes cannot wait for each other in a cycle.
   int oXA, oXD, oXB, oXW, oXS;
   int oXC;                                  // commit round: one granule per workgroup
   int oXAh, oXQ, oXP;
@@ -127,6 +145,12 @@ struct Q2Args {
   int ninl;                                 // > 0: the schedule of the call's ninl steps rides in inl (no
                                             // host-to-device upload); 0: eps / u / row0 / n_iter above
   struct { double eps, u; int64_t row0; int32_t n_iter, pad_; } inl[32];
+  // look-ahead (declared last: the kernel-argument offsets of everything above are the parent's)
+  int ahead;                                // 1: look-ahead (HMCX_P2_AHEAD): blocks [G, 2G) are a second chain team
+                                            // ("lane 1") that runs the odd steps, each under the assumption
+                                            // that the step before it rejects; help is 0 then
+  int laneoff;                              // lane 1's XA, XD, XB, XW and XS: lane 0's offsets plus this
+  int oXV;                                  // verdict records, 8 granules (one line) per workgroup and lane
 };
 constexpr int P2_NINL = 32;                 // calls of up to this many steps pass their schedule inline
 // One schedule value of step s: the kernel-argument copy (inline calls) and the global array are both
@@ -301,7 +325,9 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
             al2 = SP ? 0 : a.al2, prefetch = SP ? 1 : a.prefetch, acc1 = SP ? 1 : a.acc1,
             zoffa = SP ? 1 : a.zoff, bara = SP ? 1 : a.bar;
   // E_current and the step's momentum p0 come from helper workgroups
-  const bool hp = (SP ? HMCX_P2_HELP_DEFAULT : a.help) != 0;
+  // SPEC = 4 (5 with the segment profiler): config 2 folded with look-ahead, two chain lanes and no helpers
+  const bool ah = SP ? SPEC >= 4 : a.ahead != 0;
+  const bool hp = !ah && (SP ? HMCX_P2_HELP_DEFAULT : a.help) != 0;
   extern __shared__ __align__(16) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15;
   const int Gr = SP ? 8 : a.Gr, Gf = SP ? 16 : a.Gf, G = Gr * Gf;
@@ -310,7 +336,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   // helper G + b is the twin of chain workgroup b: same (r, f) and tile, and the same XCD whenever a team
   // region is kept in an XCD's L2 (fl2 / al2 need G % 8 == 0, so blockIdx % 8 is equal)
   const bool helper = hp && (int)blockIdx.x >= G;
-  const int pbid = helper ? (int)blockIdx.x - G : (int)blockIdx.x;
+  const int lanei = (ah && (int)blockIdx.x >= G) ? 1 : 0;              // look-ahead: the lane of this workgroup
+  const int pbid = (helper || lanei) ? (int)blockIdx.x - G : (int)blockIdx.x;
   const int bid = xmap ? (pbid & 7) * (G >> 3) + (pbid >> 3) : pbid;
   const int r = bid / Gf, f = bid - (bid / Gf) * Gf;
   const int Br = SP ? 64 : a.Br, Bf = SP ? 49 : a.Bf, BfP = SP ? 64 : a.BfP, BFP = SP ? 65 : a.BFP, Ro = SP ? 4 : a.Ro,
@@ -360,6 +387,10 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   double* stg = reinterpret_cast<double*>(profacc + 16);                             // [QSTAGE] spread gathers
   T* zbuf = reinterpret_cast<T*>(stg + QSTAGE);                                      // [Fo·KC + 16] noise
   T* pWs = zbuf + Fo * 16 + 16;                       // [BfP][16] momentum of the whole slice (bar)
+  T* Xs2 = pWs + BfP * 16;                            // look-ahead: second tile [Br][BFP] and labels [Ro][16];
+  T* Yo2 = Xs2 + (size_t)Br * BFP;                    // a step's tile stays until the step is final
+  T* Xc = Xs;                                         // tile and labels of the current step
+  T* Yc = Yo;
   // friction noise by the waves that do not poll A-RS (threads from NZ0 on), when they fit.  NZ0 comes
   // from the plan's Ro, not this member's nro: zoff decides `bar`, the protocol of round B, which every
   // workgroup must agree on — with a per-member nro, a member owning no rows (B = 40, D = 32: plan 2x2,
@@ -396,7 +427,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
 
   // segment profiler: compiled out of the config-2 instantiation (SPEC = 1); SPEC = 3 is that
   // instantiation with it (HMCX_PERSIST_PROF=1 at the config-2 shape)
-  P2Prof prof{((!SP || SPEC == 3) && bid == 0 && tid == 0 && !helper) ? a.prof : nullptr, profacc, 0ull, 0};
+  P2Prof prof{((!SP || SPEC == 3 || SPEC == 5) && bid == 0 && tid == 0 && !helper && a.prof) ? a.prof + 16 * lanei : nullptr,
+              profacc, 0ull, 0};
   // round trace: slot 2·round = payload published, 2·round + 1 = consumed (rounds A, D, B, W)
   unsigned long long* trb = (!SP && a.trace && !helper) ? a.trace + (size_t)bid * P2TR_IT * 8 : nullptr;
   auto tstamp = [&](int s_, int it_, int slot) {
@@ -412,7 +444,9 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   // Two A rounds may be in flight (the step-start round of E_current and iteration 0's): each is
   // published into region parity `par` with its own epoch (epA[par]), and consumed from the same.
   unsigned epA[2] = {0u, 0u};
-  const int oXA = helper ? a.oXAh : a.oXA;            // the helpers' A-RS rounds have a region of their own
+  const int lno = lanei ? a.laneoff : 0;              // look-ahead: lane 1's copies of the five round regions
+  const int oXA = helper ? a.oXAh : a.oXA + lno;      // the helpers' A-RS rounds have a region of their own
+  const int oXD = a.oXD + lno, oXB = a.oXB + lno, oXW = a.oXW + lno, oXS = a.oXS + lno;
   auto roundA = [&](int par) -> bool {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     epA[par] = ++ep;
@@ -422,7 +456,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     const int nkp = SP ? 13 : WPA == 1 ? (nfeat + 3) / 4 : (BfP / 4) / WPA;
     for (int item = wave; item < MTA * WPA; item += QNW) {
       const int mt = item % MTA, part = item / MTA;
-      const typename M::acc_t c = mfma_tile<T>(Xs + mt * 16 * BFP + part * nkp * 4, BFP, 1, 4,
+      const typename M::acc_t c = mfma_tile<T>(Xc + mt * 16 * BFP + part * nkp * 4, BFP, 1, 4,
                                                Wf + part * nkp * 4 * 16, 16, 64, nkp);
       if (WPA == 1) {
 #pragma unroll
@@ -620,7 +654,54 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     return;
   }
 
-  for (int s = 0; s < a.n_steps; ++s) {
+  // ---- look-ahead (ah): lane l runs the steps l, l + 2, …, each at first SPECULATIVELY from its own last
+  //      state, i.e. assuming that the twin lane's step before it leaves the state unchanged (MCMC
+  //      pre-fetching with one level).  After its accept round the lane reads the twin's verdict V(s − 1):
+  //      "unchanged" makes the run final — decision applied, outputs written, V(s) (and the new state)
+  //      published; "changed" voids it — the lane gathers the true q_s from the twin's XQ publish and runs
+  //      the step again (`redo`: not speculative, same tile, the momentum drawn again from the same
+  //      counters).  Every final run performs today's help = 0 arithmetic in today's order.
+  const int s_first = lanei, s_inc = ah ? 2 : 1;
+  bool redo = false;                                  // this run starts from the true state
+  bool pf_done = false;                               // the lane's next tile already sits in the other buffer
+  int tb = 0;                                         // tile buffer of the current step
+  const int perV = p2_pad(Fo * KC + KC, pad);         // XQ block of a feature-team member: slice + bias
+  // q after step k: the owned slices of the twin lane's feature-team members (the bias from member 0) → Wf, bsh
+  const auto gatherQ = [&](int k) -> bool {
+    const int ni = Fo * KC + KC;
+    const int base0 = a.oXQ + ((k & 1) * Gf + f) * Gr * perV;
+    const bool ok = gather_ws(rs, base0, perV, Gr, ni, [](int i) { return i; },
+                              [&](int p, int i) { return i < Fo * KC ? p * Fo + i / KC < nfeat : p == 0; },
+                              a.ep0 + (unsigned)k, a.abort_flag, [&](int q, double v) {
+      const int p = q / ni, i = q - p * ni;
+      if (i < Fo * KC) Wf[(p * Fo + i / KC) * 16 + i % KC] = (T)v;
+      else bsh[i - Fo * KC] = (T)v;
+    });
+    return all_ok(ok, ish);
+  };
+  // V(k) of the twin workgroup: one thread polls one granule with naps (a lane that waits stays off the
+  // fabric); 0 / 1 = the state was kept / changed, −1 = timed out or the abort word is up
+  const auto waitV = [&](int k) -> int {
+    if (threadIdx.x == 0) {
+      const int g = (a.oXV + ((k & 1) * G + pbid) * 8) * 16;
+      const unsigned tg = a.ep0 + (unsigned)k;
+      unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+      int res = -1;
+      for (int spins = 0;; ++spins) {
+        const gran_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, g, 0, 16 /* sc1 */);
+        if (pass_complete(gran_miss(v, tg))) { res = decode(v) != 0.0 ? 1 : 0; break; }
+        if ((spins & 63) == 63 && p2_spin_over(t0, a.abort_flag, a.oXV, tg)) break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+      ish[2] = res;
+    }
+    __syncthreads();
+    const int res = ish[2];
+    __syncthreads();
+    return res;
+  };
+
+  for (int s = s_first; s < a.n_steps;) {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     const double epsd = sched_at(inl, s, a.inl[sched_k(s)].eps, a.eps);
     const T eps = (T)epsd, ome = (T)(1.0 - epsd), nsc = (T)(2.0 * epsd);
@@ -636,7 +717,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
 
     // ---- step start: tile, labels of my rows (step 0 only: later steps' were loaded while the
     //      previous accept round travelled), momentum (hmc.py:82-87), step-start copies
-    if (s == 0 || !prefetch) load_step_rows<T>(Xs, Yo, Xg, Yg, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K, Ro, nro, ro0);
+    if ((s == s_first || !prefetch) && !redo) load_step_rows<T>(Xc, Yc, Xg, Yg, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K, Ro, nro, ro0);
     for (int e = tid; e < BfP * 16; e += QTH) Wf0[e] = Wf[e];
     if (hp) {
       // momentum (hmc.py:82-87) from the helpers: the whole slice's p0 into pWs, the bias's into pbsh / pb0sh; then the owned
@@ -710,7 +791,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
         const T e = kv ? exp(z - m) : T(0);
         const T sm = g16_sum2(e);
         const T lse = log(sm) + m;                                          // softmax.py:18
-        const double t = kv ? (double)(Yo[ii * 16 + k] * (z - lse)) : 0.0;  // softmax.py:19-20
+        const double t = kv ? (double)(Yc[ii * 16 + k] * (z - lse)) : 0.0;  // softmax.py:19-20
         const double rsum = g16_sum2(t);
         if (k == 0) rowll[ii] = rsum;
       }
@@ -783,7 +864,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
           const bool v1 = item >= nro;
           const int ii = v1 ? item - nro : item;
           const T bias = kv ? (v1 ? bpsh[k] : bsh[k]) : T(0);
-          const T y = Yo[ii * 16 + k];
+          const T y = Yc[ii * 16 + k];
           const T z = kv ? clipz(Zo[ii * 16 + k] + bias, hi, lo) : (T)-__builtin_inf();   // softmax.py:39-41
           const T m = g16_max2(z);
           const T e = kv ? exp(z - m) : T(0);                                                // softmax.py:34
@@ -808,7 +889,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       double hv = 0.0;                                  // t < KC: team colsum; t == KC: team ll
       {
         ++ep;
-        const int reg = a.oXD + (((int)(uD & 1) * Gr + r) * Gf + f) * NXA;
+        const int reg = oXD + (((int)(uD & 1) * Gr + r) * Gf + f) * NXA;
         for (int t = tid; t < NXA0; t += QTH) {
           double v;
           if (t < KC) {
@@ -825,7 +906,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
           put_t(al2, rs, reg + t, v, ep);
         }
         tstamp(s, it, 2);
-        const int base0 = a.oXD + ((int)(uD & 1) * Gr + r) * Gf * NXA;
+        const int base0 = oXD + ((int)(uD & 1) * Gr + r) * Gf * NXA;
         ++uD;
         bool ok;
         if (spread & 2) {
@@ -860,7 +941,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       prof.stamp(6);
       {
         ++ep;
-        const int reg = a.oXB + (((int)(uB & 1) * Gf + f) * Gr + r) * NXB;
+        const int reg = oXB + (((int)(uB & 1) * Gf + f) * Gr + r) * NXB;
         if (tid < HA) put_t(fl2, rs, reg + tid, hv, ep);
         // bar: the owner of an element folds its friction noise into its partial — Σ partials − 2z, so
         // ε·(−(Σ − 2z − αw)) = ε·g + 2ε·z (sghmc.py:31,34) arrives with the all-reduce and no other
@@ -871,7 +952,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
         const int nkp = (Br / 4) / WPB;
         for (int item = wave; item < MTB * WPB; item += QNW) {
           const int mt = item % MTB, part = item / MTB;
-          const typename M::acc_t c = mfma_tile<T>(Xs + part * nkp * 4 * BFP + mt * 16, 1, nkp * BFP, BFP,
+          const typename M::acc_t c = mfma_tile<T>(Xc + part * nkp * 4 * BFP + mt * 16, 1, nkp * BFP, BFP,
                                                    Ds + part * nkp * 4 * 16, nkp * 16, 16, nkp);
           if (WPB == 1) {
 #pragma unroll
@@ -893,7 +974,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
             put_t(fl2, rs, reg + HA + e, bpart(i, k, (double)v), ep);
           }
         }
-        const int base0 = a.oXB + ((int)(uB & 1) * Gf + f) * Gr * NXB;
+        const int base0 = oXB + ((int)(uB & 1) * Gf + f) * Gr * NXB;
         ++uB;
         tstamp(s, it, 4);
         prof.stamp(7);
@@ -989,11 +1070,11 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       {
         ++ep;
         const int per = p2_pad(Fo * KC, pad);
-        const int reg = a.oXW + (((int)(uW & 1) * Gf + f) * Gr + r) * per;
+        const int reg = oXW + (((int)(uW & 1) * Gf + f) * Gr + r) * per;
         if (tid < nfo * KC) put_t(fl2, rs, reg + tid, own ? (double)wv : 0.0, ep);
         tstamp(s, it, 6);
         if (own) Wf[wl] = wv;
-        const int base0 = a.oXW + ((int)(uW & 1) * Gf + f) * Gr * per;
+        const int base0 = oXW + ((int)(uW & 1) * Gf + f) * Gr * per;
         ++uW;
         if (spread & 8) {
           const int ni = Fo * KC;
@@ -1027,7 +1108,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     for (int k = 0; k < K; ++k) kb1 += (double)pbsh[k] * (double)pbsh[k];
     ++ep;
     {
-      const int reg = a.oXS + ((int)(uS & 1) * G + bid) * NXS;
+      const int reg = oXS + ((int)(uS & 1) * G + bid) * NXS;
       if (tid == 0) put(rs, reg + 0, kin0, ep);
       if (tid == 1) put(rs, reg + 1, kin1w, ep);
       if (tid == 2 && !hp) put(rs, reg + 2, ll0, ep);   // hp: this workgroup's helper wrote it
@@ -1037,13 +1118,18 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     // step (the last B-gemm and softmax ended before a barrier)
     // (measured: loading it with only the half of the workgroup that does not poll the accept round
     // is slower — 9.68 vs 9.44 µs per leapfrog: two load batches instead of one)
-    if (prefetch && s + 1 < a.n_steps) {
-      const int64_t rn = sched_at(inl, s + 1, a.inl[sched_k(s + 1)].row0, a.row0);
+    // (look-ahead: the lane's next step is s + 2, and its tile goes into the OTHER buffer — this step may
+    // have to be run again from the tile it holds; a redone step finds the next tile already loaded)
+    if (prefetch && s + s_inc < a.n_steps && !pf_done) {
+      const int sn = s + s_inc;
+      const int64_t rn = sched_at(inl, sn, a.inl[sched_k(sn)].row0, a.row0);
       const T* Xn = reinterpret_cast<const T*>(a.X) + (size_t)rn * D;
       const T* Yn = reinterpret_cast<const T*>(a.Y) + (size_t)rn * K;
-      load_step_rows<T>(Xs, Yo, Xn, Yn, Br, BfP, BFP, nrow, nfeat, row0, feat0, D, K, Ro, nro, ro0);
+      load_step_rows<T>(ah ? (tb ? Xs : Xs2) : Xs, ah ? (tb ? Yo : Yo2) : Yo, Xn, Yn, Br, BfP, BFP, nrow, nfeat, row0, feat0,
+                        D, K, Ro, nro, ro0);
+      pf_done = ah;
     }
-    const int sbase = a.oXS + (int)(uS & 1) * G * NXS;
+    const int sbase = oXS + (int)(uS & 1) * G * NXS;
     ++uS;
     double v3[3] = {0.0, 0.0, 0.0};
     if (acc1) {
@@ -1075,6 +1161,19 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       acc = sched_at(inl, s, a.inl[sched_k(s)].u, a.u) < A;
       llq = acc ? ll_last : L0;
     }
+    if (ah && s > 0 && !redo) {
+      // the twin's verdict on step s − 1 (this run assumed "state unchanged")
+      prof.stamp(12);
+      const int vprev = waitV(s - 1);
+      if (vprev < 0) return;
+      if (vprev) {
+        prof.stamp(13);
+        if (!gatherQ(s - 1)) return;
+        wv = own ? Wf[wl] : T(0);
+        redo = true;
+        continue;                                                          // step s again, from q_s
+      }
+    }
     if (!acc || n <= 0) {                                                  // keep q (sghmc.py:36-38)
       for (int e = tid; e < BfP * 16; e += QTH) Wf[e] = Wf0[e];
       wv = w0;
@@ -1105,9 +1204,44 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       if (tid < Fo * KC) put_t(fl2, rs, reg + tid, own ? (double)wv : 0.0, ep);
       else if (r == 0 && tid < Fo * KC + KC) put_t(fl2, rs, reg + tid, (double)bsh[tid - Fo * KC], ep);
     }
+    if (ah) {
+      // step s is final: the new state for the twin lane when the step changed it (also lane 1's last step,
+      // which lane 0 commits), then the verdict V(s), both tagged with the step
+      const bool changed = acc && n > 0;
+      const unsigned tg = a.ep0 + (unsigned)s;
+      if (changed && (s + 1 < a.n_steps || lanei)) {
+        const int reg = a.oXQ + (((s & 1) * Gf + f) * Gr + r) * perV;
+        if (tid < Fo * KC) put_t(fl2, rs, reg + tid, own ? (double)wv : 0.0, tg);
+        else if (r == 0 && tid < Fo * KC + KC) put_t(fl2, rs, reg + tid, (double)bsh[tid - Fo * KC], tg);
+      }
+      if (tid == 0) put(rs, a.oXV + ((s & 1) * G + pbid) * 8, changed ? 1.0 : 0.0, tg);
+      if (pf_done) {                                                       // the prefetched tile is the next step's
+        tb ^= 1;
+        Xc = tb ? Xs2 : Xs;
+        Yc = tb ? Yo2 : Yo;
+        pf_done = false;
+      }
+      redo = false;
+    }
+    s += s_inc;
   }
   prof.stamp(0);
   prof.flush();
+  if (ah) {
+    if (lanei) {                                      // lane 1 takes no part in the commit round
+      verdict.done = true;
+      return;
+    }
+    // the call's last step was lane 1's: its verdict, and the final state when it moved
+    if (a.n_steps >= 2 && !(a.n_steps & 1)) {
+      const int vlast = waitV(a.n_steps - 1);
+      if (vlast < 0) return;
+      if (vlast) {
+        if (!gatherQ(a.n_steps - 1)) return;
+        wv = own ? Wf[wl] : T(0);
+      }
+    }
+  }
   // ---- commit round: every workgroup publishes a 'done' granule; workgroup 0 gathers all G and
   //      proposes commit (or abort, when its gather times out or sees the abort word) on the launch's
   //      decision word; the others wait for the decision (bounded: on timeout they propose abort).
@@ -1206,7 +1340,19 @@ int p2_help_mode(const PersistPlan2& p, int K, int num_cus, size_t lds_max, int 
   return ok ? 2 : 0;
 }
 
-P2Layout p2_layout(const PersistPlan2& p, int K, int pad, int help) {
+// Look-ahead (HMCX_P2_AHEAD, hmcx_set_sghmc_ahead): 1 when a launch of plan p can carry a second chain
+// lane — 2·G workgroups at one per CU, the second X tile and label block in LDS, and the state gather of
+// at most 4 granules per thread — else 0 (the helper launch, or today's plain one); *lds as p2_help_mode.
+int p2_ahead_mode(const PersistPlan2& p, int K, size_t ts, int num_cus, size_t lds_max, int want, size_t* lds) {
+  const int G = p.Gr * p.Gf, KC = kc_of(K);
+  const size_t half = lds_max / 2 + 1024;
+  const size_t need = std::max(p.lds + ts * ((size_t)p.Br * p.BFP + (size_t)p.Ro * 16), half);
+  const bool ok = want == 1 && 2L * G <= num_cus && need <= lds_max && p.Gr * (p.Fo * KC + KC) <= 4 * QTH;
+  if (ok && lds) *lds = need;
+  return ok ? 1 : 0;
+}
+
+P2Layout p2_layout(const PersistPlan2& p, int K, int pad, int help, int ahead) {
   const long G = (long)p.Gr * p.Gf;
   const int KC = kc_of(K);
   P2Layout l{};
@@ -1230,7 +1376,20 @@ P2Layout p2_layout(const PersistPlan2& p, int K, int pad, int help) {
   l.oXQ = l.oXAh + l.nXAh;
   l.nXP = l.nXQ;
   l.oXP = l.oXQ + l.nXQ;
-  l.ngran = l.oXP + l.nXP;
+  l.oL1 = l.oXV = l.ngran = l.oXP + l.nXP;
+  if (ahead) {
+    // no helpers: XQ carries the accepted states between the lanes; then lane 1's copy of XA … XS (same
+    // order and sizes, so one offset serves all five) and the verdict records, a line per workgroup and lane
+    l.nXAh = l.nXP = 0;
+    l.nXQ = 2 * G * p2_pad(p.Fo * KC + KC, pad);
+    l.oXQ = l.oXAh;
+    l.oXP = l.oXQ + l.nXQ;
+    l.oL1 = l.oXP;
+    l.nL1 = l.oXC - l.oXA;
+    l.oXV = l.oL1 + l.nL1;
+    l.nXV = 2 * G * 8;
+    l.ngran = l.oXV + l.nXV;
+  }
   return l;
 }
 
@@ -1243,9 +1402,24 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   // helper workgroups (1, E_current alone, measured no gain at the 20-step shape and is not built)
   const char* help_env = getenv("HMCX_P2_HELP");
   size_t lds = pl.lds;
-  const int help = p2_help_mode(pl, K, ctx->num_cus, ctx->lds_max, help_env ? atoi(help_env) : HMCX_P2_HELP_DEFAULT,
-                                &lds);
-  const P2Layout lay = p2_layout(pl, K, pad, help);
+  // HMCX_P2_AHEAD (read per call; else the context's hmcx_set_sghmc_ahead mode): 0 off, 1 on, 2 auto — the
+  // rule below on the accept flags the caller has reported (hmcx_sghmc_ahead_note); speed only, never
+  // results.  HMCX_P2_HELP alone in the environment asks for the launch it names, without look-ahead.
+  // Calls that record the state of every step, or stamp the rounds, run without it.
+  static const bool trace_on = getenv("HMCX_P2_TRACE") && getenv("HMCX_P2_TRACE")[0] == '1';
+  const char* ahead_env = getenv("HMCX_P2_AHEAD");
+  int ahead_want = ahead_env ? atoi(ahead_env) : help_env ? 0 : ctx->sghmc_ahead;
+  if (ahead_want == 2) {
+    int acc = 0;
+    const int seen = std::min(ctx->ahead_seen, P2_AHEAD_WINDOW);
+    for (int i = 0; i < seen; ++i) acc += (int)((ctx->ahead_flags >> i) & 1ull);
+    ahead_want = ctx->ahead_on = hmcx_p2_ahead_rule(ctx->ahead_on, seen, acc);
+  }
+  if (s->out_trace || trace_on) ahead_want = 0;
+  const int ahead = p2_ahead_mode(pl, K, sizeof(T), ctx->num_cus, ctx->lds_max, ahead_want, &lds);
+  const int help = ahead ? 0 : p2_help_mode(pl, K, ctx->num_cus, ctx->lds_max,
+                                            help_env ? atoi(help_env) : HMCX_P2_HELP_DEFAULT, &lds);
+  const P2Layout lay = p2_layout(pl, K, pad, help, ahead);
   const long ngran = lay.ngran;
   if (ngran * 16 > 0x7fffffffL) return set_error(ctx, HMCX_EUNSUPPORTED, "persistent SGHMC: arena too large");
   int rc = abort_precheck(ctx);                  // an earlier launch's timeout, before enqueueing more
@@ -1265,6 +1439,9 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   unsigned rounds = 0;                           // ≤ 5 epochs per leapfrog iteration (it = -1 … L-1, accept)
   for (size_t i = 0; i < n; ++i) rounds += 5u * (unsigned)(std::max(s->n_iter[i], 0) + 2);
   rounds += 1 + (help ? 1 : 0);                  // the commit round; with helpers E(-1), the launch's first epoch
+  // look-ahead: each lane counts its own rounds from ep0 (in regions of its own) and may run each of its
+  // steps twice; the step tags ep0 + k of the verdicts lie in the same range (n_steps ≤ rounds)
+  if (ahead) rounds = 2 * rounds + 2;
   unsigned ep0 = 1;
   if ((rc = gx_epochs(ctx, rounds, &ep0))) return rc;
   Q2Args a{};
@@ -1314,14 +1491,18 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   a.oXS = (int)lay.oXS; a.oXC = (int)lay.oXC; a.oXAh = (int)lay.oXAh; a.oXQ = (int)lay.oXQ;
   a.oXP = (int)lay.oXP;
   a.help = help;
+  a.ahead = ahead;
+  a.laneoff = (int)(lay.oL1 - lay.oXA);
+  a.oXV = (int)lay.oXV;
   a.arena_bytes = (int)(ngran * 16);
   a.ep0 = ep0;
   a.pad = pad;
   static const bool dbg = getenv("HMCX_P2_DEBUG") && getenv("HMCX_P2_DEBUG")[0] == '1';
   if (dbg)
     fprintf(stderr, "[hmcx p2] B=%d D=%d K=%d plan %dx%d Br=%d Bf=%d BfP=%d Ro=%d Fo=%d; granule bases XA %d XD %d XB %d "
-            "XW %d XS %d XC %d; help %d XAh %d XQ %d XP %d; epochs %u..%u\n", s->B, s->D, K, pl.Gr, pl.Gf, pl.Br, pl.Bf,
-            pl.BfP, pl.Ro, pl.Fo, a.oXA, a.oXD, a.oXB, a.oXW, a.oXS, a.oXC, a.help, a.oXAh, a.oXQ, a.oXP, ep0, ep0 + rounds - 1);
+            "XW %d XS %d XC %d; help %d XAh %d XQ %d XP %d; ahead %d lane-1 offset %d XV %d; epochs %u..%u\n", s->B, s->D, K,
+            pl.Gr, pl.Gf, pl.Br, pl.Bf, pl.BfP, pl.Ro, pl.Fo, a.oXA, a.oXD, a.oXB, a.oXW, a.oXS, a.oXC, a.help, a.oXAh, a.oXQ,
+            a.oXP, a.ahead, a.laneoff, a.oXV, ep0, ep0 + rounds - 1);
   {
     const int HA = KC + 1;
     const bool fits = pl.Gf * pl.Ro * KC <= QSTAGE && pl.Gf * (HA + pl.Ro * KC) <= QSTAGE &&
@@ -1372,12 +1553,11 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   }
   static const bool prof_on = getenv("HMCX_PERSIST_PROF") && getenv("HMCX_PERSIST_PROF")[0] == '1';
   unsigned long long* dprof = nullptr;
-  if (prof_on) {
-    HMCX_HIP(ctx, hipMalloc((void**)&dprof, 16 * sizeof(unsigned long long)));
-    HMCX_HIP(ctx, hipMemsetAsync(dprof, 0, 16 * sizeof(unsigned long long), ctx->stream));
+  if (prof_on) {                                 // one block of 16 per lane (look-ahead: workgroups 0 and G)
+    HMCX_HIP(ctx, hipMalloc((void**)&dprof, 32 * sizeof(unsigned long long)));
+    HMCX_HIP(ctx, hipMemsetAsync(dprof, 0, 32 * sizeof(unsigned long long), ctx->stream));
   }
   a.prof = dprof;
-  static const bool trace_on = getenv("HMCX_P2_TRACE") && getenv("HMCX_P2_TRACE")[0] == '1';
   unsigned long long* dtrace = nullptr;
   const size_t ntr = (size_t)G * P2TR_IT * 8;
   if (trace_on) {
@@ -1389,20 +1569,21 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   const bool spec = sizeof(T) == 8 && KC == 10 && s->B == 500 && s->D == 784 && K == 10 && pl.Gr == 8 && pl.Gf == 16 &&
                     pl.Br == 64 && pl.Bf == 49 && pl.BfP == 64 && pl.BFP == 65 && pl.Ro == 4 && pl.Fo == 7 &&
                     a.spread == 2 && a.pad == 1 && a.xmap == 0 && a.fl2 == 1 && a.al2 == 0 && a.prefetch == 1 &&
-                    a.acc1 == 1 && a.zoff == 1 && a.bar == 1 && !a.trace && a.help == HMCX_P2_HELP_DEFAULT;
+                    a.acc1 == 1 && a.zoff == 1 && a.bar == 1 && !a.trace && (ahead || a.help == HMCX_P2_HELP_DEFAULT);
   static const bool no_spec = getenv("HMCX_P2_SPEC") && getenv("HMCX_P2_SPEC")[0] == '0';
   const void* kfn = KC == 10 ? (const void*)k_sghmc_p2<T, 10> : (const void*)k_sghmc_p2<T, 16>;
   if constexpr (sizeof(T) == 8) {                // config 2 is f64: no folded f32 kernel is built
-    if (spec && !no_spec) kfn = a.prof ? (const void*)k_sghmc_p2<T, 10, 3> : (const void*)k_sghmc_p2<T, 10, 1>;
+    if (spec && !no_spec && !ahead) kfn = a.prof ? (const void*)k_sghmc_p2<T, 10, 3> : (const void*)k_sghmc_p2<T, 10, 1>;
+    if (spec && !no_spec && ahead) kfn = a.prof ? (const void*)k_sghmc_p2<T, 10, 5> : (const void*)k_sghmc_p2<T, 10, 4>;
   }
   void* kargs[] = {&a};
   // co-residency of all workgroups (G, or 2·G at one per CU with helpers) is checked here (occupancy
   // query × CUs, cached per kernel); a plain launch then has the same residency as a cooperative one
   // without its per-launch host cost
-  const int nwg = help ? 2 * G : G;
+  const int nwg = (help || ahead) ? 2 * G : G;
   int per_cu = 0;
   if ((rc = kernel_occupancy(ctx, kfn, QTH, (int)lds, &per_cu))) return rc;
-  if ((long)per_cu * ctx->num_cus < nwg || (help && per_cu != 1))
+  if ((long)per_cu * ctx->num_cus < nwg || ((help || ahead) && per_cu != 1))
     return set_error(ctx, HMCX_EUNSUPPORTED, "persistent SGHMC: workgroups cannot be co-resident");
   // the verdict is sticky (P2Verdict): zeroed here, only a workgroup that leaves without committing
   // stores 1.  The call's output slot is idle at enqueue time (the caller collected its previous use).
@@ -1434,17 +1615,21 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   HMCX_HIP(ctx, hipMemcpyAsync(&flag, a.abort_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HMCX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (dprof) {
-    unsigned long long h[16];
-    HMCX_HIP(ctx, hipMemcpy(h, dprof, sizeof(h), hipMemcpyDeviceToHost));
+    unsigned long long hh[32];
+    HMCX_HIP(ctx, hipMemcpy(hh, dprof, sizeof(hh), hipMemcpyDeviceToHost));
     (void)hipFree(dprof);
-    unsigned long long tot = 0;
-    for (int i = 0; i < 12; ++i) tot += h[i];
-    static const char* names[12] = {"step-start", "A-gemm+publish", "noise", "A-RS wait", "softmax", "A-AG",
-                                    "B-gemm+publish", "B-RS wait", "update", "B-AG", "accept", "it=-1"};
-    fprintf(stderr, "[hmcx p2 prof] G=%dx%d Br=%d Bf=%d Ro=%d Fo=%d total %llu ticks:", pl.Gr, pl.Gf, pl.Br, pl.Bf,
-            pl.Ro, pl.Fo, tot);
-    for (int i = 0; i < 12; ++i) fprintf(stderr, " %s %.1f%%", names[i], tot ? 100.0 * h[i] / tot : 0.0);
-    fprintf(stderr, "\n");
+    static const char* names[14] = {"step-start", "A-gemm+publish", "noise", "A-RS wait", "softmax", "A-AG",
+                                    "B-gemm+publish", "B-RS wait", "update", "B-AG", "accept", "it=-1",
+                                    "verdict wait+apply", "state gather"};
+    for (int ln = 0; ln < (ahead ? 2 : 1); ++ln) {
+      const unsigned long long* h = hh + 16 * ln;
+      unsigned long long tot = 0;
+      for (int i = 0; i < 14; ++i) tot += h[i];
+      fprintf(stderr, "[hmcx p2 prof] G=%dx%d Br=%d Bf=%d Ro=%d Fo=%d lane %d total %llu ticks:", pl.Gr, pl.Gf, pl.Br,
+              pl.Bf, pl.Ro, pl.Fo, ln, tot);
+      for (int i = 0; i < 14; ++i) fprintf(stderr, " %s %.1f%%", names[i], tot ? 100.0 * h[i] / tot : 0.0);
+      fprintf(stderr, "\n");
+    }
   }
   if (dtrace) {
     std::vector<unsigned long long> h(ntr);
@@ -1509,6 +1694,38 @@ extern "C" int hmcx_p2_plan_query(int B, int D, int K, int tsize, int num_cus, l
                          l.oXQ, l.nXQ, l.oXP, l.nXP, l.ngran};
   for (int i = 0; i < 30; ++i) out[1 + i] = v[i];
   return 0;
+}
+
+// Look-ahead of the same call (hmcx_set_sghmc_ahead mode `want`, 1 = on): out[0..3] = mode (1 when the
+// launch carries two lanes), workgroups launched, launch LDS, plan LDS; out[4..25]: offset and size of XA,
+// XD, XB, XW, XS, XC, XQ, L1 (lane 1's XA … XS), XV in address order, then ngran, Br, BFP, Ro.
+extern "C" int hmcx_p2_ahead_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
+                                   long long* out) {
+  using namespace hmcx;
+  const PersistPlan2 p = plan_p2(B, D, K, (size_t)tsize, num_cus, (size_t)lds_max);
+  for (int i = 0; i < 26; ++i) out[i] = 0;
+  if (!p.ok) return 0;
+  size_t lds = p.lds;
+  const int ahead = p2_ahead_mode(p, K, (size_t)tsize, num_cus, (size_t)lds_max, want, &lds);
+  const P2Layout l = p2_layout(p, K, pad, 0, ahead);
+  const long long v[] = {ahead, (long long)(ahead ? 2 : 1) * p.Gr * p.Gf, (long long)lds, (long long)p.lds,
+                         l.oXA, l.nXA, l.oXD, l.nXD, l.oXB, l.nXB, l.oXW, l.nXW, l.oXS, l.nXS, l.oXC, l.nXC,
+                         l.oXQ, l.nXQ, l.oL1, l.nL1, l.oXV, l.nXV, l.ngran, p.Br, p.BFP, p.Ro};
+  for (int i = 0; i < 26; ++i) out[i] = v[i];
+  return 0;
+}
+
+// The auto rule of hmcx_set_sghmc_ahead(ctx, 2): the mode of the next launch from the mode `on` of the
+// last one and the accept flags of the context's last `seen` resolved steps, `accepted` of them set.
+// Fewer than P2_AHEAD_MIN steps decide nothing.  Look-ahead wins while most proposals are rejected (a
+// rejected step's successor was already running); above the break-even accept rate every accepted step
+// costs a redone one.  Two thresholds (hysteresis), derived in DESIGN §5.1 round 9.
+extern "C" int hmcx_p2_ahead_rule(int on, int seen, int accepted) {
+  if (seen < hmcx::P2_AHEAD_MIN) return on ? 1 : 0;
+  const double rate = (double)accepted / (double)seen;
+  if (on && rate > hmcx::P2_AHEAD_OFF_ABOVE) return 0;
+  if (!on && rate < hmcx::P2_AHEAD_ON_BELOW) return 1;
+  return on ? 1 : 0;
 }
 
 namespace hmcx {

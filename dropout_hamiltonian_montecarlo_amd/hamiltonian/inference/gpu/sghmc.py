@@ -332,6 +332,8 @@ class sghmc(sgmcmc):
             slot['busy'] = None
         self._inflight.remove(h)
         f = raw[:32 * nsc].view(np.float64)
+        if C == 1:                               # the look-ahead auto rule reads finished calls' flags
+            ctx.sghmc_ahead_note(raw[32 * nsc:36 * nsc].view(np.int32))
         acc = raw[32 * nsc:36 * nsc].view(np.int32).astype(bool)
         A, ll, E = f[:nsc], f[nsc:2 * nsc], f[2 * nsc:]
         steps = h['out_steps'].cpu().numpy() if h.get('out_steps') is not None else None

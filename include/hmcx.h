@@ -56,6 +56,21 @@ int hmcx_set_graph_mode(hmcx_ctx* ctx, int enabled);
 /* SGHMC implementation: 0 = auto (persistent single-launch kernel when C == 1 and the shape
  * fits, else kernel-per-phase), 1 = kernel-per-phase, 2 = persistent only (error otherwise). */
 int hmcx_set_sghmc_path(hmcx_ctx* ctx, int path);
+/* Look-ahead of the persistent single-chain SGHMC launch: 0 = off, 1 = on, 2 = auto (the default).  With
+ * look-ahead the launch carries two chain teams ("lanes") on disjoint halves of the device; step s + 1 runs
+ * at the same time as step s under the assumption that s rejects, and is run again from the true state
+ * when s accepted — every step that counts performs the same arithmetic in the same order, so results do
+ * not depend on the mode.  It pays while most proposals are rejected.  A shape where the second lane does
+ * not fit, and a call with out_trace, run without it.  Auto starts with look-ahead on and follows
+ * hmcx_p2_ahead_rule over the accept flags reported through hmcx_sghmc_ahead_note: flags of calls that
+ * have finished, handed over by the caller when it reads them, so nothing blocks (a caller that never
+ * reports stays on).  The environment variable HMCX_P2_AHEAD=<0|1|2>, read per call, overrides the mode. */
+int hmcx_set_sghmc_ahead(hmcx_ctx* ctx, int mode);
+int hmcx_sghmc_ahead_note(hmcx_ctx* ctx, const int32_t* accepted /* host [n] */, int n);
+/* The auto rule (host arithmetic only): the next launch's mode from the last launch's (`on`) and the
+ * accept flags of the last `seen` resolved steps (at most 32), `accepted` of them set.  Fewer than 16
+ * steps decide nothing; look-ahead goes off above an accept rate of 0.4 and on again below 0.3. */
+int hmcx_p2_ahead_rule(int on, int seen, int accepted);
 /* Device timing of sampler runs: when enabled, HIP events on the launch stream bracket the
  * kernels of every hmcx_sghmc_run / hmcx_sgld_run call (for the persistent SGHMC path: exactly
  * its one kernel launch).  Enabling (or disabling) resets the totals; hmcx_get_timing waits
@@ -262,6 +277,12 @@ int hmcx_philox_schedule(uint64_t seed, uint32_t chain0, int C, uint32_t step_ba
  *   XC, XAh, XQ, XP, [30] granules in the arena. */
 int hmcx_p2_plan_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
                        long long* out);
+/* The same for look-ahead mode `want` (1 = on).  out: host long long[26] — [0] 1 when the launch carries
+ * two lanes, [1] workgroups launched, [2] dynamic LDS of the launch, [3] plan LDS, [4..21] offset and size
+ * in granules of XA, XD, XB, XW, XS, XC, XQ, L1 (lane 1's XA … XS) and XV (verdict records), in address
+ * order, [22] granules in the arena, [23..25] Br, BFP, Ro. */
+int hmcx_p2_ahead_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
+                        long long* out);
 
 /* Replaces hamiltonian/inference/cpu/sgld.py:31-46 (step): p = N(0,(2ε)²) − ½ε∇U; q += p.
  * With pW/pb set: hamiltonian/inference/gpu/sgld.py:11-20, p = ν⊙p_prev − ½ε∇U with
