@@ -1553,6 +1553,38 @@ void net_init(MlpNet<T>& net, int B, int n_in, int n_mid, int n_out, hipStream_t
   net.vec_masks = n_mid % 4 == 0;
 }
 
+// an environment switch set to 0 (every HMCX_MLP_* switch is on unless its value starts with '0')
+inline bool env_off(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
+
+// mask kind of a launch (one per launch: every sub-grid reads the same kind)
+template <typename T> inline int mask_kind(const MaskSrc<T>& ms) {
+  return ms.keep ? MK_KEEP : ms.vals ? MK_VALS : MK_NONE;
+}
+// f(std::integral_constant<int, MK>): a launch site instantiates its kernel once per mask kind it can meet
+template <typename F> void with_mask_kind(int mk, F&& f) {
+  if (mk == MK_KEEP) f(std::integral_constant<int, MK_KEEP>{});
+  else if (mk == MK_VALS) f(std::integral_constant<int, MK_VALS>{});
+  else f(std::integral_constant<int, MK_NONE>{});
+}
+// the float32-only launches: fwdr_ok / quad_ok admit keep-flag and buffer masks only
+template <typename F> void with_mask_kind2(int mk, F&& f) {
+  if (mk == MK_KEEP) f(std::integral_constant<int, MK_KEEP>{});
+  else f(std::integral_constant<int, MK_VALS>{});
+}
+
+// The grids of a dual launch (k_mm2 / k_mm2b: two GEMM sub-grids side by side, z planes each): the tile
+// grid of one, and the launch grid that covers both.
+template <typename T> inline int3 tile_grid(const MMArgs<T>& a, int z) {
+  return make_int3((a.M + 31) / 32, (a.N + 31) / 32, z);
+}
+inline dim3 dual_grid(const int3& g1, const int3& g2) {
+  return dim3((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), (unsigned)(g1.z + g2.z));
+}
+inline int2 xy(const int3& g) { return make_int2(g.x, g.y); }
+
 // Launch k_mm for a call site with compile-time operand layouts (TA: A stored [K][M], TB: B stored
 // [N][K]); k-contiguous operands take the 16-byte vector path when aligned.  Takes the pending update.
 // BAT: the call site passes a problem table (k_mmb); plain call sites instantiate k_mm only.
@@ -1563,7 +1595,7 @@ void net_init(MlpNet<T>& net, int B, int n_in, int n_mid, int n_out, hipStream_t
 // (DESIGN §5.3 Round 5).  HMCX_MLP_XMAP=0 keeps the dispatch order everywhere.
 template <typename T>
 void xcd_choose(MMArgs<T>& a, int GX, int GY, int gx, int gy) {
-  static const bool off = getenv("HMCX_MLP_XMAP") && getenv("HMCX_MLP_XMAP")[0] == '0';
+  static const bool off = env_off("HMCX_MLP_XMAP");
   a.xmap = 0;
   if (off || sizeof(T) != 4 || gx * gy < 16 || (GX * GY) % 8) return;
   const int per = GX * GY / 8;                                   // positions per XCD in the plane
@@ -1622,9 +1654,7 @@ hipError_t mm(MlpNet<T>& net, MMArgs<T>& a, const MMProbs<T>* prp = nullptr) {
   constexpr bool masked = AOP == OP_H1 || BOP == OP_H1 || EPI == MM_L2 || EPI == MM_L3CE || EPI == MM_GA1 ||
                           EPI == MM_L23;
   if constexpr (!masked) go(std::integral_constant<int, MK_NONE>{});
-  else if (a.ms.keep) go(std::integral_constant<int, MK_KEEP>{});
-  else if (a.ms.vals) go(std::integral_constant<int, MK_VALS>{});
-  else go(std::integral_constant<int, MK_NONE>{});
+  else with_mask_kind(mask_kind(a.ms), go);
   return hipGetLastError();
 }
 
@@ -1701,9 +1731,9 @@ hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double
   a.pend = net.pend;
   net.pend.n = 0;
   const size_t lds = 32 * sizeof(double) + ((size_t)MM_NT + (size_t)32 * (net.n_out + 1)) * sizeof(T);
-  if (a.ms.keep) hipLaunchKernelGGL((k_l3_wide<T, MK_KEEP>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
-  else if (a.ms.vals) hipLaunchKernelGGL((k_l3_wide<T, MK_VALS>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
-  else hipLaunchKernelGGL((k_l3_wide<T, MK_NONE>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
+  with_mask_kind(mask_kind(a.ms), [&](auto mkc) {
+    hipLaunchKernelGGL((k_l3_wide<T, decltype(mkc)::value>), dim3(net.nlb), dim3(MM_NT), lds, net.st, a, (const T*)net.z);
+  });
   return hipGetLastError();
 }
 
@@ -1716,19 +1746,25 @@ hipError_t mlp_ga1(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, bool want_
   return mm<T, MM_GA1, 0, 0>(net, a);
 }
 
-// Weight gradient of W1 / W2 through the k_mm epilogue (biases and W3 come from partials).
+// Weight gradient of W1 (v = 0: ga1ᵀ·X) or W2 (v = 2: ga2ᵀ·h1, h1 from net's xw, b1 and the m0 mask) with the
+// update `mode` in the k_mm epilogue (biases and W3 come from partials): the launch arguments, and the launch.
+template <typename T>
+void wgrad_build(MlpNet<T>& net, const MaskSrc<T>& ms, const T* b1, int v, int mode, const Upd<T>& u, MMArgs<T>& a) {
+  const int B = net.B, nm = net.n_mid;
+  a = MMArgs<T>{};
+  a.upd_mode = mode; a.u = u;
+  if (v == 2) {
+    mm_set<T>(a, nm, nm, B, net.ga2, nm, 1, net.xw, nm, 0, nullptr, nm);
+    a.ms = ms; a.b1 = b1;
+  } else {
+    mm_set<T>(a, nm, net.n_in, B, net.ga1, nm, 1, net.X, net.n_in, 0, nullptr, net.n_in);
+  }
+}
 template <typename T>
 hipError_t mlp_wgrad(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, int v, int mode, const Upd<T>& u) {
-  const int B = net.B, nm = net.n_mid;
-  MMArgs<T> a{};
-  a.upd_mode = mode; a.u = u;
-  if (v == 2) {                                               // ga2ᵀ·h1
-    mm_set<T>(a, nm, nm, B, net.ga2, nm, 1, net.xw, nm, 0, nullptr, nm);
-    a.ms = ms; a.b1 = q[1];
-    return mm<T, MM_UPD, 1, 0, OP_PLAIN, OP_H1>(net, a);
-  }
-  mm_set<T>(a, nm, net.n_in, B, net.ga1, nm, 1, net.X, net.n_in, 0, nullptr, net.n_in);   // ga1ᵀ·X
-  return mm<T, MM_UPD, 1, 0>(net, a);
+  MMArgs<T> a;
+  wgrad_build(net, ms, (const T*)q[1], v, mode, u, a);
+  return v == 2 ? mm<T, MM_UPD, 1, 0, OP_PLAIN, OP_H1>(net, a) : mm<T, MM_UPD, 1, 0>(net, a);
 }
 
 // xw = X·W1ᵀ into net.xw
@@ -1821,19 +1857,10 @@ void ga1_build(MlpNet<T>& net, const SubStep<T>* const* ss, int np, MMArgs<T>& a
   a.ms = q0.ms; a.H = net.xw; a.b1 = q0.b1; a.colpart = q0.colpart;
 }
 
-// Weight gradient of W1 (v = 0: ga1ᵀ·X) or W2 (v = 2: ga2ᵀ·h1) of sub-step net `sn` with the SGHMC
-// epilogue, as mlp_wgrad.
+// The same arguments for sub-step s on its scratch net `sn`, with the SGHMC epilogue.
 template <typename T>
 void wgrad_build(MlpNet<T>& sn, const SubStep<T>& s, int v, const Upd<T>& u, MMArgs<T>& a) {
-  const int B = sn.B, nm = sn.n_mid;
-  a = MMArgs<T>{};
-  a.upd_mode = UPD_SGHMC; a.u = u;
-  if (v == 2) {
-    mm_set<T>(a, nm, nm, B, sn.ga2, nm, 1, sn.xw, nm, 0, nullptr, nm);
-    a.ms = s.ms; a.b1 = s.q[1];
-  } else {
-    mm_set<T>(a, nm, sn.n_in, B, sn.ga1, nm, 1, sn.X, sn.n_in, 0, nullptr, sn.n_in);
-  }
+  wgrad_build(sn, s.ms, (const T*)s.q[1], v, UPD_SGHMC, u, a);
 }
 
 template <typename T>
@@ -1845,11 +1872,6 @@ hipError_t mlp_forward_batch(MlpNet<T>& net, const SubStep<T>* ss, int np) {
   l23_build(net, sp, np, 0, a, pr);
   if (net.fwd_counts) ++net.fwd_counts[1];
   return mm<T, MM_L23, 0, 1, OP_H1, OP_PLAIN, true>(net, a, &pr);
-}
-
-// mask kind of a launch (one per launch: every sub-grid reads the same kind)
-template <typename T> inline int mask_kind(const MaskSrc<T>& ms) {
-  return ms.keep ? MK_KEEP : ms.vals ? MK_VALS : MK_NONE;
 }
 
 // The layer-1 backwards of np sub-steps and the W2 gradient of sub-step net `w2n` in ONE launch
@@ -1868,33 +1890,28 @@ hipError_t mlp_ga1_w2(MlpNet<T>& net, const SubStep<T>* const* ss, int np, MlpNe
   a2.pend = w2n.pend;
   w2n.pend.n = 0;
   if (mask_kind(a1.ms) != mask_kind(a2.ms)) return hipErrorInvalidValue;
-  const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, np + (a1.pend.n > 0 ? 1 : 0));
-  const int2 g2 = make_int2((a2.M + 31) / 32, (a2.N + 31) / 32);
-  const dim3 grid((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), (unsigned)(g1.z + 1));
+  const int3 g1 = tile_grid(a1, np + (a1.pend.n > 0 ? 1 : 0)), g2 = tile_grid(a2, 1);
+  const dim3 grid = dual_grid(g1, g2);
   bool aal = nm % (int)(16 / sizeof(T)) == 0;
   for (int p = 0; p < np; ++p) aal = aal && vec_ok(pr.p[p].A, nm, sizeof(T));
   hipStream_t st = net.st;
   auto go = [&](auto mkc, auto avc) {
     constexpr int MK = decltype(mkc)::value, AV = decltype(avc)::value;
     hipLaunchKernelGGL((k_mm2<T, MM_GA1, OP_PLAIN, OP_PLAIN, 0, 0, AV, 0, MM_UPD, OP_PLAIN, OP_H1, 1, 0, 0, 0, MK>),
-                       grid, dim3(MM_NT), 0, st, a1, pr, a2, g1, g2);
+                       grid, dim3(MM_NT), 0, st, a1, pr, a2, g1, xy(g2));
   };
-  auto go_mk = [&](auto mkc) {
+  with_mask_kind(mask_kind(a1.ms), [&](auto mkc) {
     if (aal) go(mkc, std::integral_constant<int, 1>{});
     else go(mkc, std::integral_constant<int, 0>{});
-  };
-  switch (mask_kind(a1.ms)) {
-    case MK_KEEP: go_mk(std::integral_constant<int, MK_KEEP>{}); break;
-    case MK_VALS: go_mk(std::integral_constant<int, MK_VALS>{}); break;
-    default: go_mk(std::integral_constant<int, MK_NONE>{}); break;
-  }
+  });
   return hipGetLastError();
 }
 
-// Four launches per iteration (fit ≥ 4 fused grids co-resident, keep-flag or buffer masks, aligned
-// operands): the fused forwards of 4 sub-steps (those of W1, b1, W2 and one more), then ONE launch of
-// the other 2 fused forwards beside the layer-1 backwards of W1 / b1 (k_mm2b), then ONE launch of the
-// W1 and W2 gradients (k_mm2, the pending bias / W3 updates in its extra plane), then layer 1.
+// The quad schedule (iter_quad), four launches per iteration (float32, fit ≥ 4 fused grids co-resident,
+// keep-flag or buffer masks, aligned operands): the fused forwards of 4 sub-steps (those of W1, b1, W2 and
+// one more), then ONE launch of the other 2 fused forwards beside the layer-1 backwards of W1 / b1
+// (mlp_l23_ga1, k_mm2b), then the W1 gradient (mlp_wgrad, the pending bias / W3 updates in its extra
+// plane), then ONE launch of the next iteration's layer 1 beside the W2 gradient (mlp_l1_w2, k_mm2).
 template <typename T>
 bool quad_ok(const MlpNet<T>& net, const SubStep<T>* ss) {
   if (sizeof(T) != 4) return false;                            // float64: two fused grids fit, not four
@@ -1915,18 +1932,15 @@ hipError_t mlp_l23_ga1(MlpNet<T>& net, const SubStep<T>* const* fw, int nf, cons
   ga1_build(net, ga, nga, a2, p2);
   a1.pend.n = 0;
   a2.pend.n = 0;
-  const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, nf);
-  const int3 g2 = make_int3((a2.M + 31) / 32, (a2.N + 31) / 32, nga);
-  const dim3 grid((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), (unsigned)(g1.z + g2.z));
+  const int3 g1 = tile_grid(a1, nf), g2 = tile_grid(a2, nga);
+  const dim3 grid = dual_grid(g1, g2);
   hipStream_t st = net.st;
   if constexpr (sizeof(T) == 4) {                              // float32 only (quad_ok)
-    auto go = [&](auto mkc) {
+    with_mask_kind2(mask_kind(a1.ms), [&](auto mkc) {
       constexpr int MK = decltype(mkc)::value;
       hipLaunchKernelGGL((k_mm2b<T, MM_L23, OP_H1, OP_PLAIN, 0, 1, 1, 1, MM_GA1, OP_PLAIN, OP_PLAIN, 0, 0, 1, 0, MK>),
                          grid, dim3(MM_NT), 0, st, a1, p1, a2, p2, g1, g2);
-    };
-    if (mask_kind(a1.ms) == MK_KEEP) go(std::integral_constant<int, MK_KEEP>{});
-    else go(std::integral_constant<int, MK_VALS>{});
+    });
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
@@ -1934,12 +1948,11 @@ hipError_t mlp_l23_ga1(MlpNet<T>& net, const SubStep<T>* const* fw, int nf, cons
 
 // k_fwdr in the batched sampler: float32 (the bench's dtype; float64 keeps the k_mm forwards), n_mid a
 // multiple of 32 up to 256, n_out ≤ 16, keep-flag or buffer masks, 16-byte aligned xw / W2 rows and
-// masks.  HMCX_MLP_FWDR=0 (read per call) keeps the k_mm fused forwards (MM_L23) — whose results the
-// one-sub-step-at-a-time order reproduces bit for bit.
+// masks.  on: the call's HMCX_MLP_FWDR switch; 0 keeps the k_mm fused forwards (MM_L23) — whose results
+// the one-sub-step-at-a-time order reproduces bit for bit.
 template <typename T>
-bool fwdr_ok(const MlpNet<T>& net, const SubStep<T>* ss, int n) {
-  const char* env = getenv("HMCX_MLP_FWDR");
-  if ((env && env[0] == '0') || sizeof(T) != 4) return false;
+bool fwdr_ok(const MlpNet<T>& net, const SubStep<T>* ss, int n, bool on) {
+  if (!on || sizeof(T) != 4) return false;
   if (net.n_mid % 32 || net.n_mid > FR_NMAX || net.n_out > 16 || !net.vec_masks || !net.fpb2) return false;
   // layer 1 in two 16-byte-aligned split-K halves; the W2 gradient in 4 row quarters whose m0 masks start
   // on a keep word
@@ -1994,9 +2007,9 @@ hipError_t mlp_fwdr(MlpNet<T>& net, const SubStep<T>* const* ss, int np, const R
   const unsigned krows = (unsigned)((kitems + per_row - 1) / per_row);
   const dim3 grid((unsigned)net.nrb, (unsigned)(np + (a.pend.n > 0 ? 1 : 0)) + krows);
   if constexpr (sizeof(T) == 4) {                              // float32 only (fwdr_ok)
-    const int mk = mask_kind(a.p[0].ms);
-    if (mk == MK_KEEP) hipLaunchKernelGGL((k_fwdr<T, MK_KEEP>), grid, dim3(FR_NW * 64), 0, net.st, a);
-    else hipLaunchKernelGGL((k_fwdr<T, MK_VALS>), grid, dim3(FR_NW * 64), 0, net.st, a);
+    with_mask_kind2(mask_kind(a.p[0].ms), [&](auto mkc) {
+      hipLaunchKernelGGL((k_fwdr<T, decltype(mkc)::value>), grid, dim3(FR_NW * 64), 0, net.st, a);
+    });
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
@@ -2048,17 +2061,14 @@ hipError_t mlp_w1_w2split(MlpNet<T>& pn0, const SubStep<T>& s1, const Upd<T>& u1
     if (x.ms.vals) x.ms.vals += r0;
   }
   a2.C = p2.p[0].C; a2.ldc = nm;
-  const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, 1 + (a1.pend.n > 0 ? 1 : 0));
-  const int3 g2 = make_int3((nm + 31) / 32, (nm + 31) / 32, 4);
-  const dim3 grid((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), (unsigned)(g1.z + g2.z));
+  const int3 g1 = tile_grid(a1, 1 + (a1.pend.n > 0 ? 1 : 0)), g2 = tile_grid(a2, 4);   // a2: n_mid × n_mid
+  const dim3 grid = dual_grid(g1, g2);
   if constexpr (sizeof(T) == 4) {                              // float32 only (the k_fwdr path)
-    auto go = [&](auto mkc) {
+    with_mask_kind2(mask_kind(a2.ms), [&](auto mkc) {
       constexpr int MK = decltype(mkc)::value;                 // the W1 gradient reads no masks
       hipLaunchKernelGGL((k_mm2b<T, MM_UPD, OP_PLAIN, OP_PLAIN, 1, 0, 0, 0, MM_STORE, OP_PLAIN, OP_H1, 1, 0, 0, 0, MK>),
                          grid, dim3(MM_NT), 0, pn0.st, a1, p1, a2, p2, g1, g2);
-    };
-    if (mask_kind(a2.ms) == MK_KEEP) go(std::integral_constant<int, MK_KEEP>{});
-    else go(std::integral_constant<int, MK_VALS>{});
+    });
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
@@ -2091,74 +2101,42 @@ hipError_t mlp_l1_w2(MlpNet<T>& net, const T* W1, T* out, MlpNet<T>& w2n, const 
   if (sizeof(T) != 4 || (mk != MK_KEEP && mk != MK_VALS) || net.n_in % 4 || !vec_ok(net.X, net.n_in, sizeof(T)) ||
       !vec_ok(W1, net.n_in, sizeof(T)))
     return hipSuccess;
-  const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, 1);
-  const int2 g2 = make_int2((a2.M + 31) / 32, (a2.N + 31) / 32);
-  const dim3 grid((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), 2u);
+  const int3 g1 = tile_grid(a1, 1), g2 = tile_grid(a2, 1);
+  const dim3 grid = dual_grid(g1, g2);
   xcd_choose<T>(a1, (int)grid.x, (int)grid.y, g1.x, g1.y);     // layer 1: 4 × 4 tile blocks per XCD
   xcd_choose<T>(a2, (int)grid.x, (int)grid.y, g2.x, g2.y);     // W2 gradient: 2 × 4
   hipStream_t st = net.st;
   if constexpr (sizeof(T) == 4) {
-    auto go = [&](auto mkc) {
+    with_mask_kind2(mk, [&](auto mkc) {
       constexpr int MK = decltype(mkc)::value;   // layer 1 reads no masks: any kind is its plain code
       hipLaunchKernelGGL((k_mm2<T, MM_STORE, OP_PLAIN, OP_PLAIN, 0, 1, 1, 1, MM_UPD, OP_PLAIN, OP_H1, 1, 0, 0, 0, MK>),
-                         grid, dim3(MM_NT), 0, st, a1, p1, a2, g1, g2);
-    };
-    if (mk == MK_KEEP) go(std::integral_constant<int, MK_KEEP>{});
-    else go(std::integral_constant<int, MK_VALS>{});
+                         grid, dim3(MM_NT), 0, st, a1, p1, a2, g1, xy(g2));
+    });
     *done = true;
   }
   return hipGetLastError();
 }
 
+// Queue the update of variable v from the partials [nparts][n] on net's next launch.  False: the launch's
+// MAXPEND slots are taken (the caller reports pend_full).
 template <typename T>
-hipError_t mlp_w1_w2(MlpNet<T>& net, MlpNet<T>& w1n, const SubStep<T>& s1, const Upd<T>& u1, MlpNet<T>& w2n,
-                     const SubStep<T>& s2, const Upd<T>& u2) {
-  MMArgs<T> a1, a2;
-  MMProbs3<T> p1{};
-  wgrad_build(w1n, s1, 0, u1, a1);
-  wgrad_build(w2n, s2, 2, u2, a2);
-  a1.pend = net.pend;
-  net.pend.n = 0;
-  a2.pend.n = 0;
-  const int3 g1 = make_int3((a1.M + 31) / 32, (a1.N + 31) / 32, 1 + (a1.pend.n > 0 ? 1 : 0));
-  const int2 g2 = make_int2((a2.M + 31) / 32, (a2.N + 31) / 32);
-  const dim3 grid((unsigned)std::max(g1.x, g2.x), (unsigned)std::max(g1.y, g2.y), (unsigned)(g1.z + 1));
-  xcd_choose<T>(a1, (int)grid.x, (int)grid.y, g1.x, g1.y);     // W1 gradient: y-major chunks
-  xcd_choose<T>(a2, (int)grid.x, (int)grid.y, g2.x, g2.y);     // W2 gradient: 2 × 4 tile blocks
-  hipStream_t st = net.st;
-  if constexpr (sizeof(T) == 4) {                              // float32 only (quad_ok)
-    auto go = [&](auto mkc) {
-      constexpr int MK = decltype(mkc)::value;   // the W1 gradient reads no masks: any kind is its plain code
-      hipLaunchKernelGGL((k_mm2<T, MM_UPD, OP_PLAIN, OP_PLAIN, 1, 0, 0, 0, MM_UPD, OP_PLAIN, OP_H1, 1, 0, 0, 0, MK>),
-                         grid, dim3(MM_NT), 0, st, a1, p1, a2, g1, g2);
-    };
-    if (mask_kind(a2.ms) == MK_KEEP) go(std::integral_constant<int, MK_KEEP>{});
-    else go(std::integral_constant<int, MK_VALS>{});
-    return hipGetLastError();
-  }
-  return hipErrorInvalidValue;
-}
-
-// Queue the update of variable v from the partials of `src` (default: net's own) on net's next launch.
-template <typename T>
-void set_pending(MlpNet<T>& net, int v, int mode, const Upd<T>& u, const MlpNet<T>* src = nullptr) {
-  if (!src) src = &net;
-  Pending<T>& p = net.pend.p[net.pend.n++];
-  p.mode = mode; p.u = u; p.nparts = net.nlb;
-  switch (v) {
-    case 1: p.part = src->pb1; p.n = net.n_mid; break;
-    case 3: p.part = src->pb2; p.n = net.n_mid; break;
-    case 4: p.part = src->pw3; p.n = net.n_out * net.n_mid; break;
-    default: p.part = src->pb3; p.n = net.n_out; break;
-  }
-}
-
-// The same from explicit partials [nparts][n] (k_fwdr's per-16-row-block partials).
-template <typename T>
-void set_pending_part(MlpNet<T>& net, int v, int mode, const Upd<T>& u, const T* part, int nparts) {
+bool set_pending_part(MlpNet<T>& net, int v, int mode, const Upd<T>& u, const T* part, int nparts) {
+  if (net.pend.n == MAXPEND) return false;
   Pending<T>& p = net.pend.p[net.pend.n++];
   p.mode = mode; p.u = u; p.nparts = nparts; p.part = part;
   p.n = net.nvar(v);
+  return true;
+}
+
+// The same for a bias or W3 (v = 1, 3, 4, 5) from the 32-row-block partials of `src` (default: net's own).
+template <typename T>
+bool set_pending(MlpNet<T>& net, int v, int mode, const Upd<T>& u, const MlpNet<T>* src = nullptr) {
+  if (!src) src = &net;
+  return set_pending_part(net, v, mode, u, v == 1 ? src->pb1 : v == 3 ? src->pb2 : v == 4 ? src->pw3 : src->pb3, net.nlb);
+}
+
+inline int pend_full(hmcx_ctx* ctx) {
+  return set_error(ctx, HMCX_EINVAL, "mlp: more than 4 pending updates queued on one launch");
 }
 
 template <typename T>
@@ -2178,7 +2156,7 @@ hipError_t flush_pending(MlpNet<T>& net) {
 // The arena holds `regions` equal parts: a batched fused launch gives problem p region p.
 template <typename T>
 int net_fuse(hmcx_ctx* ctx, MlpNet<T>& net, int regions = 1) {
-  static const bool off = getenv("HMCX_MLP_FUSE") && getenv("HMCX_MLP_FUSE")[0] == '0';
+  static const bool off = env_off("HMCX_MLP_FUSE");
   const int S = (net.n_mid + 31) / 32;
   if (off || ctx->mlp_nofuse || net.n_out > 32 || S > 16) return HMCX_OK;
   int per_cu = 0;
@@ -2225,6 +2203,38 @@ void mlp_workspace(Workspace& ws, MlpNet<T>& net) {
   net.pw3 = ws.take<T>((size_t)net.nlb * net.n_out * net.n_mid);
 }
 
+// The net of a one-off call (gradient, loss, HMC trajectory): unfused — no exchange that could time out —
+// with its workspace, loss partials and the caller's mask buffer (null: no masks).
+template <typename T>
+int oneoff_net(hmcx_ctx* ctx, Workspace& ws, MlpNet<T>& net, const void* X, const int32_t* y, int B, int n_in, int n_mid,
+               int n_out, const void* masks, double** lpart, MaskSrc<T>* ms) {
+  net_init(net, B, n_in, n_mid, n_out, ctx->stream);
+  net.X = (const T*)X; net.y = y;
+  do { ws.reset(); mlp_workspace<T>(ws, net); *lpart = ws.take<double>(net.nlb); } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  *ms = MaskSrc<T>{(const T*)masks, nullptr, T(1), B * n_mid};
+  if (masks && (uintptr_t)masks % 16) net.vec_masks = false;
+  return HMCX_OK;
+}
+
+// Profiling dumps (HMCX_MLP_PROF, HMCX_FWDR_PROF): wait for the call, copy its n stamps from the device and
+// let `records` append them to the file as records of an int header followed by stamps.
+inline void prof_record(FILE* f, std::initializer_list<int> hdr, const unsigned long long* stamps, size_t n) {
+  fwrite(hdr.begin(), sizeof(int), hdr.size(), f);
+  fwrite(stamps, sizeof(unsigned long long), n, f);
+}
+template <typename F>
+int prof_append(hmcx_ctx* ctx, hipStream_t st, const char* path, const unsigned long long* dev, size_t n, F&& records) {
+  HMCX_HIP(ctx, hipStreamSynchronize(st));
+  std::vector<unsigned long long> h(n);
+  HMCX_HIP(ctx, hipMemcpy(h.data(), dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(path, "ab")) {
+    records(f, (const unsigned long long*)h.data());
+    fclose(f);
+  }
+  return HMCX_OK;
+}
+
 }  // namespace
 
 template <typename T>
@@ -2241,14 +2251,10 @@ template <typename T>
 int mlp_grad_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, int n_mid, int n_out,
                const hmcx_mlp_params* par, const void* masks, double alpha, hmcx_mlp_params* grads, double* loss) {
   MlpNet<T> net{};
-  net_init(net, B, n_in, n_mid, n_out, ctx->stream);
-  net.X = (const T*)X; net.y = y;          // one-off calls run unfused: no exchange that could time out
   Workspace ws(ctx);
   double* lpart;
-  do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
-  if (ws.failed) return HMCX_ENOMEM;
-  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid};
-  if (masks && (uintptr_t)masks % 16) net.vec_masks = false;
+  MaskSrc<T> ms;
+  if (int rc = oneoff_net<T>(ctx, ws, net, X, y, B, n_in, n_mid, n_out, masks, &lpart, &ms)) return rc;
   T* q[6];
   for (int v = 0; v < 6; ++v) q[v] = (T*)par->p[v];
   HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, lpart, L3Want{true, true, true, true}));
@@ -2261,7 +2267,7 @@ int mlp_grad_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, 
   }
   for (int v : {1, 3, 4, 5}) {
     u.W = q[v]; u.G = (T*)grads->p[v];
-    set_pending(net, v, UPD_GRAD, u);
+    if (!set_pending(net, v, UPD_GRAD, u)) return pend_full(ctx);
     HMCX_HIP(ctx, flush_pending(net));
   }
   if (loss) {
@@ -2279,15 +2285,11 @@ int mlp_grad_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, 
 template <typename T>
 int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
   MlpNet<T> net{};
-  net_init(net, s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
-  net.X = (const T*)s->X; net.y = s->y;                       // unfused (see mlp_grad_t)
   Workspace ws(ctx);
   double* lpart;
-  do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
-  if (ws.failed) return HMCX_ENOMEM;
+  MaskSrc<T> ms;
   const void* mptr = s->mask_mode == HMCX_MLP_MASKS_NONE ? nullptr : s->masks;
-  const MaskSrc<T> ms{(const T*)mptr, nullptr, T(1), s->B * s->n_mid};
-  if (mptr && (uintptr_t)mptr % 16) net.vec_masks = false;
+  if (int rc = oneoff_net<T>(ctx, ws, net, s->X, s->y, s->B, s->n_in, s->n_mid, s->n_out, mptr, &lpart, &ms)) return rc;
   T *q[6], *p[6], *g[6];
   int64_t dim[6];
   for (int v = 0; v < 6; ++v) {
@@ -2317,7 +2319,7 @@ int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
     for (int v : {1, 3, 4, 5})
       if (want & (1u << v)) {
         u.W = q[v]; u.G = g[v];
-        set_pending(net, v, UPD_GRAD, u);
+        if (!set_pending(net, v, UPD_GRAD, u)) return pend_full(ctx);
       }
     if (!defer) HMCX_HIP(ctx, flush_pending(net));            // else: the next kicks launch applies them
     return HMCX_OK;
@@ -2337,7 +2339,15 @@ int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
       k.slot = slot++;
       n = std::max(n, (int64_t)(k.n3 + 63) / 64);
     }
-    k.ps = net.pend;                                           // the previous call's deferred bias / W3 gradients
+    // the previous call's deferred bias / W3 gradients: the launch applies those its kicks read (g of pu or
+    // nv); any other would be dropped, so it is applied first, in a launch of its own
+    bool read_here = true;
+    for (int j = 0; j < net.pend.n; ++j) {
+      const Pending<T>& pd = net.pend.p[j];
+      read_here = read_here && pd.mode == UPD_GRAD && (pd.u.G == k.gu || pd.u.G == k.gv);
+    }
+    if (!read_here) HMCX_HIP(ctx, flush_pending(net));
+    k.ps = net.pend;
     net.pend.n = 0;
     if (n == 0) return HMCX_OK;
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
@@ -2374,14 +2384,10 @@ template <typename T>
 int mlp_loss_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, int n_mid, int n_out,
                const hmcx_mlp_params* par, const void* masks, double* loss, void* logits) {
   MlpNet<T> net{};
-  net_init(net, B, n_in, n_mid, n_out, ctx->stream);
-  net.X = (const T*)X; net.y = y;          // unfused (see mlp_grad_t)
   Workspace ws(ctx);
   double* lpart;
-  do { ws.reset(); mlp_workspace<T>(ws, net); lpart = ws.take<double>(net.nlb); } while (ws.retry());
-  if (ws.failed) return HMCX_ENOMEM;
-  const MaskSrc<T> ms{(const T*)masks, nullptr, T(1), B * n_mid};
-  if (masks && (uintptr_t)masks % 16) net.vec_masks = false;
+  MaskSrc<T> ms;
+  if (int rc = oneoff_net<T>(ctx, ws, net, X, y, B, n_in, n_mid, n_out, masks, &lpart, &ms)) return rc;
   T* q[6];
   for (int v = 0; v < 6; ++v) q[v] = (T*)par->p[v];
   HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, y ? lpart : nullptr, L3Want{false, false, false, false}, (T*)logits));
@@ -2397,158 +2403,230 @@ int mlp_loss_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, 
   return HMCX_OK;
 }
 
+// ------------------------------------------------------------------ hmcx_mlp_sghmc_run
+// The pieces of mlp_sghmc_t (below): validate, plan, then per step the start launch, the leapfrog iterations
+// on ONE of four host schedules (iter_fwdr / iter_quad / iter_chunked / iter_single; DESIGN §5.3 "Host
+// schedules" has their eligibility and launches), the energy forwards and the accept test.  The object is
+// the call context: the net and its scratch nets, the layout of the variables, the switches (each read once
+// per call, in validate) and every workspace pointer (plan).
+namespace {
 template <typename T>
-int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
-  MlpNet<T> net{};
-  net_init(net, s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
-  if (int rc0 = net_fuse<T>(ctx, net, MAXPROB)) return rc0;
-  net.fwd_counts = ctx->mlp_fwd_counts;
-  const int mn = s->B * s->n_mid, n3 = 3 * mn;
-  int off_v[6], dim[6], P = 0;                                // element offset of each variable in `order`
-  {
-    int seen = 0;
-    for (int i = 0; i < 6; ++i) {
+struct MlpSghmc {
+  hmcx_ctx* ctx;
+  const hmcx_mlp_sghmc_args* s;
+  hipStream_t stream = nullptr;
+  MlpNet<T> net{}, pn[6]{}, en[2]{};                         // pn: one per sub-step; en: gz of E_new / E_current
+  int off_v[6], dim[6], P = 0;                               // element offset of each variable in `order`
+  int mn = 0, n3 = 0, kw = 0, maxF = 2;                      // B·n_mid; mask elements, keep words per forward
+  bool philox_masks = false, batch = false, keep_split_on = true, fwdr_on = true;
+  T *par[6], *pv[6], *qa[6], *qb[6], *qc[6];
+  T *xw_own = nullptr, *xw_b1 = nullptr, *xw_par = nullptr; // xw of even / odd iterations, of the start state
+  T *xwp[2] = {}, *xpar[2] = {}, *w2part = nullptr;         // k_fwdr path: layer-1 split-K planes, W2 partials
+  double *part_cur, *part_new, *lp_cur, *lp_new, *lp_scr;
+  uint32_t* keep = nullptr;                                  // keep flags of the step: one bit per element
+  int32_t* accf = nullptr;
+  const char *prof_path = nullptr, *fr_prof_path = nullptr;
+  bool commit_pending = false;                               // the previous step's proposal awaits its commit
+  T* prev_prop[6] = {};
+  // Batched: positions of iteration it (−1: the start state) in the (it % 3)-th of three sets: its sub-steps
+  // read iterations it and it − 1 and write it + 1, so three sets never alias within an iteration (the pending
+  // bias / W3 updates then run beside readers of it − 1).  Its xw in one of two: the next iteration's layer 1
+  // may run beside this iteration's W2 gradient, which reads this iteration's xw.
+  T* const* pos(int it) const { return it < 0 ? par : it % 3 == 0 ? qa : it % 3 == 1 ? qb : qc; }
+  T* xwb(int it) const { return (it & 1) ? xw_b1 : xw_own; }
+  // One leapfrog iteration: its positions and, on the batched schedules, its six sub-steps.
+  struct Iter {
+    int it;
+    bool last;                                                 // no iteration follows in this step
+    T* const* Xit; T* const* Xpr; T* const* Xnx;               // positions of iterations it, it − 1, it + 1
+    SubStep<T> ss[6];
+    const SubStep<T>* ga[6];                                   // the sub-steps with a layer-1 backward (W1, b1)
+    int nga = 0, i2 = 0;                                       // i2: position of the W2 sub-step
+    T* next(int v) const { return last ? nullptr : Xnx[v]; }  // where v's next position goes (none after the last)
+  };
+  // Fixed for a step, and the state that evolves through it.
+  struct Step {
+    const MlpSghmc* c;
+    int si, n, F;                                              // F: forwards of the step, 6n + 2
+    double eps;
+    uint32_t step_id;
+    const double* nz;                                          // BUFFER noise of the step (null: Philox)
+    bool batched = false, fr_step = false, keep_split = false;
+    T* cur[6];                                                 // the proposal's positions so far
+    int fwd = 0;                                               // one at a time: forwards run so far
+    bool l1_done = false;                                      // quad: the last launch carried the next layer 1
+    // batched: the E_new / E_current forwards (step_begin), which rode along, which by k_fwdr
+    SubStep<T> es[2];
+    bool e_done[2] = {false, false}, e_fr[2] = {false, false};
+    // masks of forward f of the step: its stored keep flags (Philox), or the caller's values
+    MaskSrc<T> masks_for(int f) const {
+      const T scale = (T)(1.0 / 0.9);
+      if (c->philox_masks) return MaskSrc<T>{nullptr, c->keep + (size_t)f * c->kw, scale, c->mn};
+      return MaskSrc<T>{(const T*)c->s->masks + c->s->mask_off[si] + (size_t)f * c->n3, nullptr, scale, c->mn};
+    }
+    // the SGHMC update of variable v in iteration x
+    Upd<T> upd_for(const Iter& x, int v) const {
+      const hmcx_mlp_sghmc_args* s = c->s;
+      Upd<T> u{};
+      u.W = x.Xit[v]; u.P = c->pv[v]; u.Qn = x.next(v);
+      u.half_alpha = (T)(0.5 * s->alpha); u.eps = (T)eps; u.one_minus_eps = (T)(1.0 - eps);
+      u.noise_scale = (T)(2.0 * eps);
+      u.noise_mode = s->noise_mode;
+      u.noise = nz ? nz + (size_t)c->P * (x.it + 1) + c->off_v[v] : nullptr;   // BUFFER: one block of P per iteration
+      u.seed = s->seed; u.chain = s->chain; u.step = step_id; u.slot = (uint32_t)(x.it + 1);
+      u.e0 = (uint32_t)c->off_v[v];
+      return u;
+    }
+  };
+  using IterFn = int (MlpSghmc::*)(Step&, Iter&);
+
+  int validate() {
+    net_init(net, s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
+    if (int rc = net_fuse<T>(ctx, net, MAXPROB)) return rc;
+    net.fwd_counts = ctx->mlp_fwd_counts;
+    mn = s->B * s->n_mid; n3 = 3 * mn; kw = (n3 + 31) / 32;
+    for (int i = 0, seen = 0; i < 6; ++i) {
       const int v = s->order[i];
       if (v < 0 || v > 5 || ((seen >> v) & 1))
         return set_error(ctx, HMCX_EINVAL, "mlp sghmc: order must be a permutation of 0..5");
       seen |= 1 << v;
-      off_v[v] = P;
-      dim[v] = net.nvar(v);
-      P += dim[v];
+      off_v[v] = P; dim[v] = net.nvar(v); P += dim[v];
+      par[v] = (T*)s->par.p[v];
     }
-  }
-  int maxF = 2;
-  for (int si = 0; si < s->n_steps; ++si) {
-    if (s->n_iter[si] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sghmc: n_iter < 0");
-    // the step-start launch has one grid row per forward of the step (gridDim.y = 6 + 6·n_iter + 2,
-    // capped at 65535 by the hardware)
-    if (s->n_iter[si] > (65535 - 8) / 6)
-      return set_error(ctx, HMCX_EINVAL, "mlp sghmc: n_iter above 10921 leapfrog iterations per step");
-    maxF = std::max(maxF, 6 * s->n_iter[si] + 2);
-  }
-  const bool philox_masks = s->mask_mode == HMCX_NOISE_PHILOX;
-  // A step's masks come from one of two sources: the caller's buffer (MK_VALS), or — Philox masks — the
-  // step's keep flags, drawn once (k_mlp_start / k_mlp_keep / k_fwdr's free rows) and loaded by every
-  // kernel that reads them (MK_KEEP).  No kernel here draws its own flags: the draws would sit on the
-  // layer-2 GEMM's critical path.
-  const char* ks_env = getenv("HMCX_MLP_KEEP_SPLIT");
-  const bool keep_split_on = !(ks_env && ks_env[0] == '0');
-  // Batched iterations.  Sub-step i of leapfrog iteration it (variable v = order[i]) evaluates the
-  // gradient at q_u(it) for the variables at order positions u ≤ i and q_u(it − 1) for the others
-  // (sghmc.py:29-34: each variable is drifted just before its own gradient call) and moves only v's
-  // momentum and v's NEXT position — so it needs iteration it − 1 complete and nothing of iteration it:
-  // the six sub-steps of one iteration are independent.  With W1 first (one xw per iteration), an
-  // iteration is: layer 1 (+ the previous iteration's bias / W3 updates in its prologue), the six fused
-  // forwards in one launch (or in chunks of what fits co-resident), the W1 / b1 layer-1 backwards in
-  // one launch, the W1 and W2 gradients with their SGHMC epilogues — 5 launches instead of 11.  Same
-  // kernels, operands, masks and noise as the one-at-a-time order: identical results.
-  // HMCX_MLP_BATCH=0 runs the sub-steps one at a time.
-  const char* batch_env = getenv("HMCX_MLP_BATCH");             // read per call (tests switch it)
-  const bool batch_off = batch_env && batch_env[0] == '0';
-  const bool batch = !batch_off && net.fuse && s->order[0] == 0 && net.l23_fit >= 1;
-  MlpNet<T> pn[6]{};
-  MlpNet<T> en[2]{};                                           // scratch (gz) of the E_new / E_current forwards
-  if (philox_masks) {
-    if (n3 % 4) net.vec_masks = false;
-  } else {
-    if ((uintptr_t)s->masks % 16 || ((size_t)n3 * sizeof(T)) % 16) net.vec_masks = false;
-    for (int si = 0; si < s->n_steps; ++si)
-      if ((s->mask_off[si] * sizeof(T)) % 16) net.vec_masks = false;
-  }
-  Workspace ws(ctx);
-  T *pv[6], *qa[6], *qb[6], *qc[6], *xw_par = nullptr, *xw_b1 = nullptr;
-  T *xwp[2] = {}, *xpar[2] = {}, *w2part = nullptr;           // k_fwdr path: layer-1 split-K planes, W2 partials
-  double *part_cur, *part_new, *lp_cur, *lp_new, *lp_scr;
-  uint32_t* keep = nullptr;                                  // keep flags of the step: one bit per element
-  const int kw = (n3 + 31) / 32;                              // words per forward
-  int32_t* accf;
-  static const char* prof_path = getenv("HMCX_MLP_PROF");
-  static const char* fr_prof_path = getenv("HMCX_FWDR_PROF");
-  const int prof_cap = prof_path && net.fuse ? 8192 : 0;
-  do {
-    ws.reset();
-    mlp_workspace<T>(ws, net);
-    for (int i = 0; i < 6 && batch; ++i) {
-      net_init(pn[i], s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
-      mlp_workspace<T>(ws, pn[i]);
-      pn[i].lpart_scr = ws.take<double>(net.nlb);
-      pn[i].fpb2 = ws.take<T>((size_t)net.nrb * s->n_mid);       // k_fwdr's 16-row-block partials
-      pn[i].fpw3 = ws.take<T>((size_t)net.nrb * s->n_out * s->n_mid);
-      pn[i].fpb3 = ws.take<T>((size_t)net.nrb * s->n_out);
+    for (int si = 0; si < s->n_steps; ++si) {
+      if (s->n_iter[si] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sghmc: n_iter < 0");
+      // the step-start launch has one grid row per forward of the step (gridDim.y = 6 + 6·n_iter + 2,
+      // capped at 65535 by the hardware)
+      if (s->n_iter[si] > (65535 - 8) / 6)
+        return set_error(ctx, HMCX_EINVAL, "mlp sghmc: n_iter above 10921 leapfrog iterations per step");
+      maxF = std::max(maxF, 6 * s->n_iter[si] + 2);
     }
-    net.fpb2 = batch ? pn[0].fpb2 : nullptr;                       // marks the buffers as present (fwdr_ok)
-    net.prof = prof_cap ? ws.take<unsigned long long>((size_t)prof_cap * net.nlb * ((net.n_mid + 31) / 32) * L23_NPH)
-                        : nullptr;
+    // A step's masks come from one of two sources: the caller's buffer (MK_VALS), or — Philox masks — the
+    // step's keep flags, drawn once (k_mlp_start / k_mlp_keep / k_fwdr's free rows) and loaded by every
+    // kernel that reads them (MK_KEEP).  No kernel here draws its own flags: the draws would sit on the
+    // layer-2 GEMM's critical path.
+    philox_masks = s->mask_mode == HMCX_NOISE_PHILOX;
+    if (philox_masks) {
+      if (n3 % 4) net.vec_masks = false;
+    } else {
+      if ((uintptr_t)s->masks % 16 || ((size_t)n3 * sizeof(T)) % 16) net.vec_masks = false;
+      for (int si = 0; si < s->n_steps; ++si)
+        if ((s->mask_off[si] * sizeof(T)) % 16) net.vec_masks = false;
+    }
+    // The switches, read per call (tests switch them).  Batched iterations: sub-step i of iteration it
+    // (variable v = order[i]) evaluates the gradient at q_u(it) for the variables at order positions u ≤ i and
+    // q_u(it − 1) for the others (sghmc.py:29-34: each variable is drifted just before its own gradient call)
+    // and moves only v's momentum and v's NEXT position — it needs iteration it − 1 complete and nothing of
+    // iteration it, so the six sub-steps of an iteration are independent and, with W1 first (one xw per
+    // iteration), share launches: same arithmetic, operands, masks and noise as one at a time, identical results.
+    batch = !env_off("HMCX_MLP_BATCH") && net.fuse && s->order[0] == 0 && net.l23_fit >= 1;
+    fwdr_on = !env_off("HMCX_MLP_FWDR");
+    keep_split_on = !env_off("HMCX_MLP_KEEP_SPLIT");
+    return HMCX_OK;
+  }
+
+  int plan(Workspace& ws) {
+    static const char* const paths[2] = {getenv("HMCX_MLP_PROF"), getenv("HMCX_FWDR_PROF")};   // read once
+    prof_path = paths[0]; fr_prof_path = paths[1];
+    net.prof_cap = prof_path && net.fuse ? 8192 : 0;
     net.fr_prof_cap = fr_prof_path ? 512 : 0;
     net.fr_prof_np.assign(net.fr_prof_cap, 0);
-    net.fr_prof = fr_prof_path ? ws.take<unsigned long long>((size_t)512 * net.nrb * FR_MAXP * FR_NPH) : nullptr;
-    net.prof_cap = prof_cap;
-    for (int v = 0; v < 6; ++v) {
-      pv[v] = ws.take<T>(dim[v]); qa[v] = ws.take<T>(dim[v]); qb[v] = ws.take<T>(dim[v]);
-      qc[v] = batch ? ws.take<T>(dim[v]) : nullptr;
-    }
-    if (batch) {
-      xw_par = ws.take<T>((size_t)mn);
-      xw_b1 = ws.take<T>((size_t)mn);
-      for (int h = 0; h < 2; ++h) { xwp[h] = ws.take<T>((size_t)mn); xpar[h] = ws.take<T>((size_t)mn); }
-      w2part = ws.take<T>((size_t)4 * s->n_mid * s->n_mid);
-      for (auto& e : en) e.gz = ws.take<T>((size_t)s->B * s->n_out);
-    }
-    part_cur = ws.take<double>(12 * NPART);
-    part_new = ws.take<double>(12 * NPART);
-    lp_cur = ws.take<double>(std::max(net.nlb, net.nrb));        // 32-row (k_mm) or 16-row (k_fwdr) partials
-    lp_new = ws.take<double>(std::max(net.nlb, net.nrb));
-    lp_scr = ws.take<double>(net.nlb);
-    if (philox_masks) keep = ws.take<uint32_t>((size_t)maxF * kw);
-    accf = ws.take<int32_t>(1);
-  } while (ws.retry());
-  if (ws.failed) return HMCX_ENOMEM;
-  begin_call(ctx);
-  int rc = timing_begin(ctx, ctx->stream);
-  if (rc) return rc;
-  GraphScope gs(ctx);
-  hipStream_t st = ctx->stream;
-  net.st = st;
-  T* par[6];
-  for (int v = 0; v < 6; ++v) par[v] = (T*)s->par.p[v];
-  const T* Xall = (const T*)s->X;
-  const T scale = (T)(1.0 / 0.9);
-  bool commit_pending = false;                                // the previous step's proposal awaits its commit
-  T* prev_prop[6] = {};
+    do {
+      ws.reset();
+      mlp_workspace<T>(ws, net);
+      for (int i = 0; i < 6 && batch; ++i) {
+        net_init(pn[i], s->B, s->n_in, s->n_mid, s->n_out, ctx->stream);
+        mlp_workspace<T>(ws, pn[i]);
+        pn[i].lpart_scr = ws.take<double>(net.nlb);
+        pn[i].fpb2 = ws.take<T>((size_t)net.nrb * s->n_mid);     // k_fwdr's 16-row-block partials
+        pn[i].fpw3 = ws.take<T>((size_t)net.nrb * s->n_out * s->n_mid);
+        pn[i].fpb3 = ws.take<T>((size_t)net.nrb * s->n_out);
+      }
+      net.fpb2 = batch ? pn[0].fpb2 : nullptr;                   // marks the buffers as present (fwdr_ok)
+      const size_t nprof = (size_t)net.prof_cap * net.nlb * ((net.n_mid + 31) / 32) * L23_NPH;
+      net.prof = nprof ? ws.take<unsigned long long>(nprof) : nullptr;
+      net.fr_prof = fr_prof_path ? ws.take<unsigned long long>((size_t)512 * net.nrb * FR_MAXP * FR_NPH) : nullptr;
+      for (int v = 0; v < 6; ++v) {
+        pv[v] = ws.take<T>(dim[v]); qa[v] = ws.take<T>(dim[v]); qb[v] = ws.take<T>(dim[v]);
+        qc[v] = batch ? ws.take<T>(dim[v]) : nullptr;
+      }
+      if (batch) {
+        xw_par = ws.take<T>((size_t)mn);
+        xw_b1 = ws.take<T>((size_t)mn);
+        for (int h = 0; h < 2; ++h) { xwp[h] = ws.take<T>((size_t)mn); xpar[h] = ws.take<T>((size_t)mn); }
+        w2part = ws.take<T>((size_t)4 * s->n_mid * s->n_mid);
+        for (auto& e : en) e.gz = ws.take<T>((size_t)s->B * s->n_out);
+      }
+      part_cur = ws.take<double>(12 * NPART);
+      part_new = ws.take<double>(12 * NPART);
+      lp_cur = ws.take<double>(std::max(net.nlb, net.nrb));      // 32-row (k_mm) or 16-row (k_fwdr) partials
+      lp_new = ws.take<double>(std::max(net.nlb, net.nrb));
+      lp_scr = ws.take<double>(net.nlb);
+      if (philox_masks) keep = ws.take<uint32_t>((size_t)maxF * kw);
+      accf = ws.take<int32_t>(1);
+    } while (ws.retry());
+    xw_own = net.xw;
+    return ws.failed ? HMCX_ENOMEM : HMCX_OK;
+  }
 
-  for (int si = 0; si < s->n_steps; ++si) {
-    net.X = Xall + (size_t)s->row0[si] * s->n_in;
+  void step_begin(int si, Step& st) {
+    net.X = (const T*)s->X + (size_t)s->row0[si] * s->n_in;
     net.y = s->y + s->row0[si];
     net.xw_valid = false;
-    const double eps = s->eps[si];
-    const int n = s->n_iter[si], F = 6 * n + 2;
-    const uint32_t step_id = s->step_base + (uint32_t)si;
-    const double* nz = s->noise_mode == HMCX_NOISE_BUFFER ? s->noise + s->noise_off[si] : nullptr;
-    // masks of forward f of the step: its stored keep flags (Philox), or the caller's values
-    auto masks_for = [&](int f) -> MaskSrc<T> {
-      if (philox_masks) return MaskSrc<T>{nullptr, keep + (size_t)f * kw, scale, mn};
-      return MaskSrc<T>{(const T*)s->masks + s->mask_off[si] + (size_t)f * n3, nullptr, scale, mn};
-    };
-    // the k_fwdr path for this step's iterations (decided before the momentum launch, which draws fewer
-    // keep flags when k_fwdr draws the later iterations')
-    bool fr_step = false;
-    if (batch && n > 0) {
-      SubStep<T> chk[6];
-      for (int i = 0; i < 6; ++i) {
-        for (int j = 0; j < 6; ++j) chk[i].q[s->order[j]] = j <= i ? qa[s->order[j]] : par[s->order[j]];
-        chk[i].xw = xw_par;
-        chk[i].ms = masks_for(0);
-      }
-      fr_step = fwdr_ok(net, chk, 6);
+    st.c = this; st.si = si; st.eps = s->eps[si];
+    st.n = s->n_iter[si]; st.F = 6 * st.n + 2;
+    st.step_id = s->step_base + (uint32_t)si;
+    st.nz = s->noise_mode == HMCX_NOISE_BUFFER ? s->noise + s->noise_off[si] : nullptr;
+    st.batched = batch && st.n > 0;
+    for (int v = 0; v < 6; ++v) st.cur[v] = par[v];
+    if (!st.batched) return;
+    // the k_fwdr path for this step's iterations, on iteration 0's positions with the start state's xw and
+    // forward 0's masks (decided before the start launch, which draws fewer keep flags when k_fwdr draws the
+    // later iterations': only iteration 0's and the two energy forwards'; HMCX_MLP_KEEP_SPLIT=0: all of them)
+    Iter x0;
+    iter_begin(st, 0, x0);
+    for (SubStep<T>& y : x0.ss) { y.xw = xw_par; y.ms = st.masks_for(0); }
+    st.fr_step = fwdr_ok(net, x0.ss, 6, fwdr_on);
+    st.keep_split = philox_masks && st.fr_step && st.n > 1 && keep_split_on;
+    for (int i = 0; i < 6; ++i) { pn[i].X = net.X; pn[i].y = net.y; pn[i].vec_masks = net.vec_masks; }
+    // The energy forwards (hmc.py:67-71): E_new at the last iteration's positions with forward 6n's masks,
+    // E_current at the start state with forward 6n + 1's.  Both only need what is known when the last
+    // (first) iteration starts, so a schedule with room lets them ride in that iteration's forward launch
+    // (energy_ride); energies_rest runs the others after the iterations.
+    for (int e = 0; e < 2; ++e) {
+      SubStep<T>& x = st.es[e];
+      x.xw = e == 0 ? xwb(st.n - 1) : xw_par;
+      for (int v = 0; v < 6; ++v) x.q[v] = e == 0 ? pos(st.n - 1)[v] : par[v];
+      x.ms = st.masks_for(6 * st.n + e);
+      x.scr = &en[e];
+      x.lpart = e == 0 ? lp_new : lp_cur;
+      x.w = L3Want{false, false, false, false};
+      x.v = -1;
     }
-    // Philox masks: the keep flags of every forward of the step in the momentum launch (compute-bound Philox
-    // draws: drawn instead beside each iteration's last launch, in an extra plane, they lengthened that
-    // launch by as much as they took off this one — 21.46 k vs 22.2 k leapfrog/s at config 3).
-    // On the k_fwdr path the step-start launch draws only iteration 0's flags and the two energy forwards';
-    // each iteration's k_fwdr draws the next iteration's in rows of its own, on the CUs its problems leave free
-    // (HMCX_MLP_KEEP_SPLIT=0: all at step start)
-    const bool keep_split = philox_masks && fr_step && n > 1 && keep_split_on;
-    // momentum (hmc.py:82-87), first drift into qa, Σp², Σθ² of the current state
+  }
+  // planes: k_fwdr sums its layer 1 from these two split-K planes and leaves 16-row loss partials
+  const SubStep<T>* energy_ride(Step& st, int e, T* const* planes = nullptr) {
+    if (planes) { st.es[e].xw = planes[0]; st.es[e].xw2 = planes[1]; st.e_fr[e] = true; }
+    st.e_done[e] = true;
+    return &st.es[e];
+  }
+  int energies_rest(Step& st) {
+    for (int v = 0; v < 6; ++v) st.cur[v] = pos(st.n - 1)[v];
+    SubStep<T> rest[2];                                        // each names its xw; one launch when both fit
+    int nr = 0;
+    for (int e = 0; e < 2; ++e)
+      if (!st.e_done[e]) rest[nr++] = st.es[e];
+    const int fit = std::min(MAXPROB, net.l23_fit);
+    for (int e0 = 0; e0 < nr; e0 += fit) HMCX_HIP(ctx, mlp_forward_batch<T>(net, rest + e0, std::min(fit, nr - e0)));
+    net.xw = xw_own;                                       // the net's own buffer again
+    return HMCX_OK;
+  }
+
+  // The step-start launch: momentum (hmc.py:82-87), first drift into qa, Σp², Σθ² of the current state, the
+  // previous step's commit folded in, and — Philox masks — the keep flags of the step's forwards (compute-bound
+  // Philox draws: drawn instead beside each iteration's last launch, in an extra plane, they lengthened that
+  // launch by as much as they took off this one — 21.46 k vs 22.2 k leapfrog/s at config 3).
+  void step_start(Step& st) {
     VarTab vt{};
     for (int i = 0; i < 6; ++i) {
       const int v = s->order[i];
@@ -2557,258 +2635,221 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     }
     const int32_t* prev_acc = commit_pending ? accf : nullptr;   // the previous step's commit, folded in
     commit_pending = false;
+    const int n = st.n, drift = n > 0 ? 1 : 0;
     if (philox_masks) {
       // forwards 0 … 5 and the energies 6n, 6n + 1 when split, else all F
-      const KeepRange kr = keep_split ? KeepRange{8, 0, 6, 6 * n} : KeepRange{F, 0, F, 0};
-      const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);        // one keep group per thread
+      const KeepRange kr = st.keep_split ? KeepRange{8, 0, 6, 6 * n} : KeepRange{st.F, 0, st.F, 0};
+      const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);      // one keep group per thread
       const unsigned rows = (unsigned)((items + (size_t)NPART * 256 - 1) / ((size_t)NPART * 256));
-      hipLaunchKernelGGL(k_mlp_start<T>, dim3(NPART, 6 + rows), dim3(256), 0, st, vt, (T)eps,
-                         n > 0 ? 1 : 0, s->noise_mode, nz, s->seed, s->chain, step_id, part_cur, prev_acc, keep, n3, kr);
+      hipLaunchKernelGGL(k_mlp_start<T>, dim3(NPART, 6 + rows), dim3(256), 0, stream, vt, (T)st.eps, drift, s->noise_mode,
+                         st.nz, s->seed, s->chain, st.step_id, part_cur, prev_acc, keep, n3, kr);
     } else {
-      hipLaunchKernelGGL(k_mlp_init<T>, dim3(NPART, 6), dim3(256), 0, st, vt, (T)eps, n > 0 ? 1 : 0, s->noise_mode,
-                         nz, s->seed, s->chain, step_id, part_cur, prev_acc);
+      hipLaunchKernelGGL(k_mlp_init<T>, dim3(NPART, 6), dim3(256), 0, stream, vt, (T)st.eps, drift, s->noise_mode, st.nz,
+                         s->seed, s->chain, st.step_id, part_cur, prev_acc);
     }
-    T* cur[6];
-    for (int v = 0; v < 6; ++v) cur[v] = par[v];
-    int fwd = 0;
-    bool e_fr[2] = {false, false};                            // E_new / E_current by k_fwdr (16-row partials)
-    auto upd_for = [&](int it, int v, T* W, T* Qn) {
-      Upd<T> u{};
-      u.W = W; u.P = pv[v]; u.Qn = Qn;
-      u.half_alpha = (T)(0.5 * s->alpha); u.eps = (T)eps; u.one_minus_eps = (T)(1.0 - eps);
-      u.noise_scale = (T)(2.0 * eps);
-      u.noise_mode = s->noise_mode;
-      u.noise = nz ? nz + (size_t)P * (it + 1) + off_v[v] : nullptr;   // BUFFER: one block of P per iteration
-      u.seed = s->seed; u.chain = s->chain; u.step = step_id; u.slot = (uint32_t)(it + 1);
-      u.e0 = (uint32_t)off_v[v];
-      return u;
-    };
-    if (batch && n > 0) {
-      // positions of iteration it in q3[it % 3]: the sub-steps of iteration it read iterations it and
-      // it − 1 and write it + 1, so three sets never alias within an iteration (the pending updates of
-      // the bias / W3 sub-steps then run beside readers of it − 1)
-      T* const* q3[3] = {qa, qb, qc};
-      // as many fused forwards per launch as fit co-resident (f32 at config 3: 4 at two workgroups per
-      // CU; three per CU with the registers spilled measured slower: one 6-problem launch 47.8 µs vs
-      // 23.8 + 17.4 for 4 + 2)
-      const int fit = std::min(MAXPROB, net.l23_fit);
-      for (int i = 0; i < 6; ++i) {
-        pn[i].X = net.X; pn[i].y = net.y; pn[i].xw = net.xw; pn[i].vec_masks = net.vec_masks;
-      }
-      // energies (hmc.py:67-71): E_new at the last iteration's positions with forward 6n's masks,
-      // E_current at the start state with forward 6n + 1's.  Both only need what is known when the
-      // last (first) iteration starts, so they ride in its second launch when there is room
-      // xw of iteration it in xwb[it & 1]: the next iteration's layer 1 may run beside this
-      // iteration's W2 gradient, which reads this iteration's xw
-      T* const xwb[2] = {net.xw, xw_b1};
-      SubStep<T> es[2];
-      bool e_done[2] = {false, false};
-      bool l1_done = false;
-      T* const* Xlast = q3[(n - 1) % 3];
-      for (int e = 0; e < 2; ++e) {
-        SubStep<T>& x = es[e];
-        x.xw = e == 0 ? xwb[(n - 1) & 1] : xw_par;
-        for (int v = 0; v < 6; ++v) x.q[v] = e == 0 ? Xlast[v] : par[v];
-        x.ms = masks_for(6 * n + e);
-        x.scr = &en[e];
-        x.lpart = e == 0 ? lp_new : lp_cur;
-        x.w = L3Want{false, false, false, false};
-        x.v = -1;
-      }
-      bool use_fr = false;                                     // the k_fwdr path (decided in iteration 0)
-      for (int it = 0; it < n; ++it) {
-        T* const* Xit = q3[it % 3];                              // positions of iteration it
-        T* const* Xpr = it == 0 ? par : q3[(it + 2) % 3];        // of iteration it − 1
-        T* const* Xnx = q3[(it + 1) % 3];                        // the next iteration's (written here)
-        net.xw = xwb[it & 1];
-        for (int i = 0; i < 6; ++i) pn[i].xw = net.xw;
-        SubStep<T> ss[6];
-        const SubStep<T>* ga[6];
-        int nga = 0;
-        for (int i = 0; i < 6; ++i) {
-          const int v = s->order[i];
-          SubStep<T>& x = ss[i];
-          x.xw = nullptr;
-          for (int j = 0; j < 6; ++j) x.q[s->order[j]] = j <= i ? Xit[s->order[j]] : Xpr[s->order[j]];
-          x.ms = masks_for(6 * it + i);
-          x.scr = &pn[i];
-          x.lpart = pn[i].lpart_scr;
-          x.w = L3Want{v <= 3, v == 3, v == 5, v == 4};
-          x.v = v;
-          if (v <= 1) ga[nga++] = &ss[i];
-        }
-        int i2 = 0;                                              // position of the W2 sub-step
-        while (s->order[i2] != 2) ++i2;
-        if (it == 0) {
-          SubStep<T> chk[8];
-          for (int i = 0; i < 6; ++i) chk[i] = ss[i];
-          chk[6] = es[0];
-          chk[7] = es[1];
-          use_fr = fr_step && fwdr_ok(net, chk, 8);
-          if (keep_split && !use_fr) {                          // the k_mm forwards: draw the rest now
-            const KeepRange kr{6 * n - 6, 6, 6 * n - 6, 0};
-            const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);
-            hipLaunchKernelGGL(k_mlp_keep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, keep, n3, kr,
-                               s->seed, s->chain, step_id);
-          }
-        }
-        if (use_fr) {
-          // 4 launches per iteration, the layer-1 GEMM and the W2 gradient as split-K partials:
-          //  A  k_fwdr: every forward of the iteration (and the energy forwards due) — h1 from the two
-          //     layer-1 planes, whose sum problem 0 stores as the iteration's xw;
-          //  B  the W1 / b1 layer-1 backwards;
-          //  C  the W1 gradient (SGHMC epilogue) + the W2 gradient as 4 row-quarter partials, the pending
-          //     bias / W3 updates in the extra plane;
-          //  D  the next iteration's layer 1 (two split-K planes) with the W2 update from its 4 partials in
-          //     the extra plane (after the last iteration: flushed before the kinetic energies).
-          if (it == 0) {                                          // layer 1 of iteration 0 and of the start state
-            const T* w1[2] = {qa[0], par[0]};
-            T* const out[2][2] = {{xwp[0], xwp[1]}, {xpar[0], xpar[1]}};
-            HMCX_HIP(ctx, mlp_layer1_split<T>(net, w1, out, 2));
-          }
-          const SubStep<T>* fa[FR_MAXP];
-          int na = 0;
-          for (int i = 0; i < 6; ++i) {
-            ss[i].xw = xwp[0];
-            ss[i].xw2 = xwp[1];
-            fa[na++] = &ss[i];
-          }
-          ss[0].xwout = net.xw;
-          if (it == n - 1) {
-            es[0].xw = xwp[0];
-            es[0].xw2 = xwp[1];
-            fa[na++] = &es[0];
-            e_done[0] = e_fr[0] = true;
-          }
-          if (it == 0) {
-            es[1].xw = xpar[0];
-            es[1].xw2 = xpar[1];
-            fa[na++] = &es[1];
-            e_done[1] = e_fr[1] = true;
-          }
-          RbFwdArgs<T> kf{};                                    // the next iteration's flags, in k_fwdr's free rows
-          if (keep_split && it + 1 < n) {
-            kf.keep = keep; kf.n3 = n3; kf.kr = KeepRange{6, 6 * (it + 1), 6, 0};
-            kf.seed = s->seed; kf.chain = s->chain; kf.step = step_id;
-          }
-          HMCX_HIP(ctx, mlp_fwdr<T>(net, fa, na, &kf));
-          HMCX_HIP(ctx, mlp_ga1_batch<T>(net, ga, nga));
-          for (int i = 0; i < 6; ++i) {
-            const int v = s->order[i];
-            if (v == 0 || v == 2) continue;
-            const Upd<T> u = upd_for(it, v, Xit[v], it + 1 < n ? Xnx[v] : nullptr);
-            if (v == 1) set_pending(pn[0], v, UPD_SGHMC, u, &pn[i]);   // b1: the layer-1 backward's 32-row partials
-            else set_pending_part(pn[0], v, UPD_SGHMC, u, v == 3 ? pn[i].fpb2 : v == 4 ? pn[i].fpw3 : pn[i].fpb3,
-                                  net.nrb);
-          }
-          HMCX_HIP(ctx, mlp_w1_w2split<T>(pn[0], ss[0], upd_for(it, 0, Xit[0], it + 1 < n ? Xnx[0] : nullptr),
-                                          pn[i2], ss[i2], w2part));
-          set_pending_part(net, 2, UPD_SGHMC, upd_for(it, 2, Xit[2], it + 1 < n ? Xnx[2] : nullptr), w2part, 4);
-          if (it + 1 < n) {
-            const T* w1[1] = {Xnx[0]};
-            T* const out[1][2] = {{xwp[0], xwp[1]}};
-            HMCX_HIP(ctx, mlp_layer1_split<T>(net, w1, out, 1));
-          }
-          fwd += 6;
-          continue;
-        }
-        if (it == 0) {                                           // xw(0) and the start state's xw (E_current)
-          const T* w1[2] = {qa[0], par[0]};
-          T* out[2] = {net.xw, xw_par};
-          HMCX_HIP(ctx, mlp_layer1_batch<T>(net, w1, out, 2));
-        } else if (!l1_done) {
-          HMCX_HIP(ctx, mlp_layer1<T>(net, Xit[0]));
-        }
-        l1_done = false;
-        if (quad_ok(net, ss)) {
-          // 4 launches: forwards of W1, b1, W2 (+ one more) | the other two forwards + the W1 / b1
-          // layer-1 backwards | the W1 and W2 gradients + every pending update | layer 1
-          const SubStep<T>* fa[6];
-          const SubStep<T>* fb[6];
-          int na = 0, nb = 0;
-          for (int i = 0; i < 6; ++i)
-            if (s->order[i] <= 2) fa[na++] = &ss[i];
-          for (int i = 0; i < 6; ++i)
-            if (s->order[i] > 2) {
-              if (na < 4) fa[na++] = &ss[i];
-              else fb[nb++] = &ss[i];
-            }
-          if (it == n - 1) { fb[nb++] = &es[0]; e_done[0] = true; }
-          if (it == 0 && n > 1) { fb[nb++] = &es[1]; e_done[1] = true; }
-          MMArgs<T> a;
-          MMProbs<T> pr{};
-          l23_build(net, fa, na, 0, a, pr);
-          ctx->mlp_fwd_counts[1] += 2;                           // both launches carry batched fused forwards
-          HMCX_HIP(ctx, (mm<T, MM_L23, 0, 1, OP_H1, OP_PLAIN, true>(net, a, &pr)));
-          HMCX_HIP(ctx, mlp_l23_ga1<T>(net, fb, nb, ga, nga));
-          // the W1 gradient with every pending bias / W3 update in its extra plane; then the next
-          // iteration's layer 1 beside this iteration's W2 gradient (which needs neither)
-          for (int i = 0; i < 6; ++i) {
-            const int v = s->order[i];
-            if (v != 0 && v != 2) set_pending(pn[0], v, UPD_SGHMC, upd_for(it, v, Xit[v], it + 1 < n ? Xnx[v] : nullptr), &pn[i]);
-          }
-          HMCX_HIP(ctx, mlp_wgrad<T>(pn[0], ss[0].q, ss[0].ms, 0, UPD_SGHMC,
-                                     upd_for(it, 0, Xit[0], it + 1 < n ? Xnx[0] : nullptr)));
-          const Upd<T> u2 = upd_for(it, 2, Xit[2], it + 1 < n ? Xnx[2] : nullptr);
-          if (it + 1 < n) HMCX_HIP(ctx, mlp_l1_w2<T>(net, Xnx[0], xwb[(it + 1) & 1], pn[i2], ss[i2], u2, &l1_done));
-          if (!l1_done) HMCX_HIP(ctx, mlp_wgrad<T>(pn[i2], ss[i2].q, ss[i2].ms, 2, UPD_SGHMC, u2));
-          fwd += 6;
-          continue;
-        }
-        for (int i0 = 0; i0 < 6; i0 += fit) HMCX_HIP(ctx, mlp_forward_batch<T>(net, ss + i0, std::min(fit, 6 - i0)));
-        // bias / W3 updates from their partials: b2, W3, b3 (partials of the fused forwards) in the
-        // layer-1 backward launch, b1 (whose partials that launch makes) in the W1 gradient launch
-        for (int i = 0; i < 6; ++i) {
-          const int v = s->order[i];
-          if (v == 0 || v == 2) continue;
-          set_pending(v == 1 ? pn[0] : net, v, UPD_SGHMC, upd_for(it, v, Xit[v], it + 1 < n ? Xnx[v] : nullptr), &pn[i]);
-        }
-        HMCX_HIP(ctx, mlp_ga1_w2<T>(net, ga, nga, pn[i2], ss[i2], upd_for(it, 2, Xit[2], it + 1 < n ? Xnx[2] : nullptr)));
-        HMCX_HIP(ctx, mlp_wgrad<T>(pn[0], ss[0].q, ss[0].ms, 0, UPD_SGHMC,
-                                   upd_for(it, 0, Xit[0], it + 1 < n ? Xnx[0] : nullptr)));
-        fwd += 6;
-      }
-      for (int v = 0; v < 6; ++v) cur[v] = q3[(n - 1) % 3][v];
-      // the energies that did not ride along (each names its xw), in one launch (xw holds the last iteration's xw)
-      SubStep<T> rest[2];
-      int nr = 0;
-      for (int e = 0; e < 2; ++e)
-        if (!e_done[e]) rest[nr++] = es[e];
-      for (int e0 = 0; e0 < nr; e0 += fit) HMCX_HIP(ctx, mlp_forward_batch<T>(net, rest + e0, std::min(fit, nr - e0)));
-      fwd += 2;
-      net.xw = xwb[0];                                         // the net's own buffer again
+  }
+
+  // Iteration it of a step: its positions and, batched, its six sub-steps (sub-step i: the variables at order
+  // positions ≤ i at iteration it, the others at it − 1) on this iteration's xw.
+  void iter_begin(Step& st, int it, Iter& x) {
+    const int* order = s->order;
+    x.it = it; x.last = it + 1 == st.n;
+    if (!st.batched) {                                         // one at a time: two sets in turn
+      x.Xit = (it & 1) ? qb : qa; x.Xnx = (it & 1) ? qa : qb; x.Xpr = nullptr;
+      return;
     }
-    for (int it = 0; it < n && !batch; ++it) {
-      for (int i = 0; i < 6; ++i) {
-        const int v = s->order[i];
-        cur[v] = (it & 1) ? qb[v] : qa[v];                    // drifted position of this iteration
-        if (v == 0) net.xw_valid = false;
-        const MaskSrc<T> ms = masks_for(fwd++);
-        const Upd<T> u = upd_for(it, v, cur[v], it + 1 < n ? ((it & 1) ? qa[v] : qb[v]) : nullptr);
-        const L3Want w{v <= 3, v == 3, v == 5, v == 4};
-        HMCX_HIP(ctx, mlp_forward<T>(net, cur, ms, lp_scr, w));
-        if (v <= 1) HMCX_HIP(ctx, mlp_ga1<T>(net, cur, ms, v == 1));
-        if (v == 0 || v == 2) HMCX_HIP(ctx, mlp_wgrad<T>(net, cur, ms, v, UPD_SGHMC, u));
-        else set_pending(net, v, UPD_SGHMC, u);
+    x.Xit = pos(it); x.Xpr = pos(it - 1); x.Xnx = pos(it + 1);
+    net.xw = xwb(it);
+    for (int i = 0; i < 6; ++i) {
+      const int v = order[i];
+      SubStep<T>& y = x.ss[i];
+      pn[i].xw = net.xw;
+      y.xw = nullptr;
+      for (int j = 0; j < 6; ++j) y.q[order[j]] = j <= i ? x.Xit[order[j]] : x.Xpr[order[j]];
+      y.ms = st.masks_for(6 * it + i);
+      y.scr = &pn[i];
+      y.lpart = pn[i].lpart_scr;
+      y.w = L3Want{v <= 3, v == 3, v == 5, v == 4};
+      y.v = v;
+      if (v <= 1) x.ga[x.nga++] = &y;
+      if (v == 2) x.i2 = i;
+    }
+  }
+
+  // Queue the SGHMC updates of the four small variables (b1, b2, W3, b3) of iteration x from their gradient
+  // partials: b1 — the layer-1 backward's 32-row partials — on t1's next launch, the others on t's, from
+  // k_fwdr's 16-row-block partials (fr) or the fused k_mm forwards' 32-row ones.
+  int queue_small(Step& st, Iter& x, MlpNet<T>& t1, MlpNet<T>& t, bool fr) {
+    for (int i = 0; i < 6; ++i) {
+      const int v = s->order[i];
+      if (v == 0 || v == 2) continue;
+      const MlpNet<T>& src = pn[i];
+      const Upd<T> u = st.upd_for(x, v);
+      const bool ok = v == 1 || !fr ? set_pending(v == 1 ? t1 : t, v, UPD_SGHMC, u, &src)
+                                    : set_pending_part(t, v, UPD_SGHMC, u, v == 3 ? src.fpb2 : v == 4 ? src.fpw3 : src.fpb3,
+                                                       net.nrb);
+      if (!ok) return pend_full(ctx);
+    }
+    return HMCX_OK;
+  }
+
+  // Schedule fwdr, 4 launches, the layer-1 GEMM and the W2 gradient as split-K partials: k_fwdr (every forward
+  // of the iteration and the energy forwards due; h1 from the two layer-1 planes, whose sum problem 0 stores as
+  // the iteration's xw; the next iteration's keep flags) | the W1 / b1 layer-1 backwards | the W1 gradient + the
+  // W2 gradient as 4 row-quarter partials, the pending bias / W3 updates in the extra plane | the next layer 1
+  // with the W2 update from its partials in the extra plane (after the last: flushed before the kinetic energies)
+  int iter_fwdr(Step& st, Iter& x) {
+    if (x.it == 0) {                                           // layer 1 of iteration 0 and of the start state
+      const T* w1[2] = {qa[0], par[0]};
+      T* const out[2][2] = {{xwp[0], xwp[1]}, {xpar[0], xpar[1]}};
+      HMCX_HIP(ctx, mlp_layer1_split<T>(net, w1, out, 2));
+    }
+    const SubStep<T>* fa[FR_MAXP];
+    int na = 0;
+    for (int i = 0; i < 6; ++i) {
+      x.ss[i].xw = xwp[0];
+      x.ss[i].xw2 = xwp[1];
+      fa[na++] = &x.ss[i];
+    }
+    x.ss[0].xwout = net.xw;
+    if (x.last) fa[na++] = energy_ride(st, 0, xwp);
+    if (x.it == 0) fa[na++] = energy_ride(st, 1, xpar);
+    RbFwdArgs<T> kf{};                                         // the next iteration's flags, in k_fwdr's free rows
+    if (st.keep_split && !x.last) {
+      kf.keep = keep; kf.n3 = n3; kf.kr = KeepRange{6, 6 * (x.it + 1), 6, 0};
+      kf.seed = s->seed; kf.chain = s->chain; kf.step = st.step_id;
+    }
+    HMCX_HIP(ctx, mlp_fwdr<T>(net, fa, na, &kf));
+    HMCX_HIP(ctx, mlp_ga1_batch<T>(net, x.ga, x.nga));
+    if (int rc = queue_small(st, x, pn[0], pn[0], true)) return rc;
+    HMCX_HIP(ctx, mlp_w1_w2split<T>(pn[0], x.ss[0], st.upd_for(x, 0), pn[x.i2], x.ss[x.i2], w2part));
+    if (!set_pending_part(net, 2, UPD_SGHMC, st.upd_for(x, 2), w2part, 4)) return pend_full(ctx);
+    if (!x.last) {
+      const T* w1[1] = {x.Xnx[0]};
+      T* const out[1][2] = {{xwp[0], xwp[1]}};
+      HMCX_HIP(ctx, mlp_layer1_split<T>(net, w1, out, 1));
+    }
+    return HMCX_OK;
+  }
+
+  // Layer 1 of the k_mm schedules: iteration 0's xw together with the start state's (E_current reads it); a
+  // later iteration's unless the previous iteration's last launch carried it.
+  int iter_layer1(Step& st, Iter& x) {
+    if (x.it == 0) {
+      const T* w1[2] = {qa[0], par[0]};
+      T* out[2] = {net.xw, xw_par};
+      HMCX_HIP(ctx, mlp_layer1_batch<T>(net, w1, out, 2));
+    } else if (!st.l1_done) {
+      HMCX_HIP(ctx, mlp_layer1<T>(net, x.Xit[0]));
+    }
+    st.l1_done = false;
+    return HMCX_OK;
+  }
+
+  // Schedule quad (quad_ok), 4 launches: the fused forwards of 4 sub-steps | the other 2 (and the energy forwards
+  // due) + the W1 / b1 layer-1 backwards | the W1 gradient, every pending bias / W3 update in its extra plane | the
+  // next layer 1 beside this iteration's W2 gradient (after the last, or operands unaligned: that gradient alone)
+  int iter_quad(Step& st, Iter& x) {
+    const int* order = s->order;
+    if (int rc = iter_layer1(st, x)) return rc;
+    const SubStep<T>* fa[6];
+    const SubStep<T>* fb[6];
+    int na = 0, nb = 0;
+    for (int i = 0; i < 6; ++i)                                // W1, b1, W2 first: the second launch reads their ga2
+      if (order[i] <= 2) fa[na++] = &x.ss[i];
+    for (int i = 0; i < 6; ++i)
+      if (order[i] > 2) {
+        if (na < 4) fa[na++] = &x.ss[i];
+        else fb[nb++] = &x.ss[i];
       }
+    if (x.last) fb[nb++] = energy_ride(st, 0);
+    if (x.it == 0 && st.n > 1) fb[nb++] = energy_ride(st, 1);
+    MMArgs<T> a;
+    MMProbs<T> pr{};
+    l23_build(net, fa, na, 0, a, pr);
+    ctx->mlp_fwd_counts[1] += 2;                               // both launches carry batched fused forwards
+    HMCX_HIP(ctx, (mm<T, MM_L23, 0, 1, OP_H1, OP_PLAIN, true>(net, a, &pr)));
+    HMCX_HIP(ctx, mlp_l23_ga1<T>(net, fb, nb, x.ga, x.nga));
+    if (int rc = queue_small(st, x, pn[0], pn[0], false)) return rc;
+    HMCX_HIP(ctx, mlp_wgrad<T>(pn[0], x.ss[0].q, x.ss[0].ms, 0, UPD_SGHMC, st.upd_for(x, 0)));
+    const SubStep<T>& s2 = x.ss[x.i2];
+    const Upd<T> u2 = st.upd_for(x, 2);
+    if (!x.last) HMCX_HIP(ctx, mlp_l1_w2<T>(net, x.Xnx[0], xwb(x.it + 1), pn[x.i2], s2, u2, &st.l1_done));
+    if (!st.l1_done) HMCX_HIP(ctx, mlp_wgrad<T>(pn[x.i2], s2.q, s2.ms, 2, UPD_SGHMC, u2));
+    return HMCX_OK;
+  }
+
+  // Schedule chunked: layer 1 | the six fused forwards in launches of as many as fit co-resident (f32 at config 3:
+  // 4; one 6-problem launch with spilled registers measured 47.8 µs vs 23.8 + 17.4) | the W1 / b1 layer-1 backwards
+  // + the W2 gradient (b2 / W3 / b3 updates in the extra plane) | the W1 gradient (b1's update in its extra plane)
+  int iter_chunked(Step& st, Iter& x) {
+    if (int rc = iter_layer1(st, x)) return rc;
+    const int fit = std::min(MAXPROB, net.l23_fit);
+    for (int i0 = 0; i0 < 6; i0 += fit) HMCX_HIP(ctx, mlp_forward_batch<T>(net, x.ss + i0, std::min(fit, 6 - i0)));
+    if (int rc = queue_small(st, x, pn[0], net, false)) return rc;
+    HMCX_HIP(ctx, mlp_ga1_w2<T>(net, x.ga, x.nga, pn[x.i2], x.ss[x.i2], st.upd_for(x, 2)));
+    HMCX_HIP(ctx, mlp_wgrad<T>(pn[0], x.ss[0].q, x.ss[0].ms, 0, UPD_SGHMC, st.upd_for(x, 0)));
+    return HMCX_OK;
+  }
+
+  // Schedule one at a time: per sub-step its forward, the layer-1 backward (W1, b1) and the W1 / W2 gradient; a
+  // bias / W3 update waits for the next launch.  Then its energies (hmc.py:67-71: E_new first, then
+  // E_current), each with fresh masks.
+  int iter_single(Step& st, Iter& x) {
+    for (int i = 0; i < 6; ++i) {
+      const int v = s->order[i];
+      st.cur[v] = x.Xit[v];                                    // drifted position of this iteration
+      if (v == 0) net.xw_valid = false;
+      const MaskSrc<T> ms = st.masks_for(st.fwd++);
+      HMCX_HIP(ctx, mlp_forward<T>(net, st.cur, ms, lp_scr, L3Want{v <= 3, v == 3, v == 5, v == 4}));
+      if (v <= 1) HMCX_HIP(ctx, mlp_ga1<T>(net, st.cur, ms, v == 1));
+      if (v == 0 || v == 2) HMCX_HIP(ctx, mlp_wgrad<T>(net, st.cur, ms, v, UPD_SGHMC, st.upd_for(x, v)));
+      else if (!set_pending(net, v, UPD_SGHMC, st.upd_for(x, v))) return pend_full(ctx);
     }
-    // energies (hmc.py:67-71: E_new first, then E_current), each with fresh masks
-    if (!(batch && n > 0)) {
-      HMCX_HIP(ctx, mlp_forward<T>(net, cur, masks_for(fwd++), lp_new, L3Want{false, false, false, false}));
-      net.xw_valid = false;
-      HMCX_HIP(ctx, mlp_forward<T>(net, par, masks_for(fwd++), lp_cur, L3Want{false, false, false, false}));
+    return HMCX_OK;
+  }
+  int energies_single(Step& st) {
+    const L3Want none{false, false, false, false};
+    HMCX_HIP(ctx, mlp_forward<T>(net, st.cur, st.masks_for(st.fwd++), lp_new, none));
+    net.xw_valid = false;
+    HMCX_HIP(ctx, mlp_forward<T>(net, par, st.masks_for(st.fwd++), lp_cur, none));
+    return HMCX_OK;
+  }
+
+  // The schedule of a step, chosen once: one at a time when not batched; k_fwdr when the step-start check
+  // (fr_step) and iteration 0's own sub-steps and energy forwards pass fwdr_ok; else quad when iteration 0's
+  // sub-steps pass quad_ok (later iterations read workspace buffers, aligned alike); else chunked.  A step that
+  // planned split keep flags for k_fwdr and does not run it draws the rest of them here.
+  IterFn pick(Step& st) {
+    if (!st.batched) return &MlpSghmc::iter_single;
+    Iter x;
+    iter_begin(st, 0, x);
+    SubStep<T> chk[8] = {x.ss[0], x.ss[1], x.ss[2], x.ss[3], x.ss[4], x.ss[5], st.es[0], st.es[1]};
+    if (st.fr_step && fwdr_ok(net, chk, 8, fwdr_on)) return &MlpSghmc::iter_fwdr;
+    if (st.keep_split) {
+      const KeepRange kr{6 * st.n - 6, 6, 6 * st.n - 6, 0};
+      const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);
+      hipLaunchKernelGGL(k_mlp_keep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, keep, n3, kr,
+                         s->seed, s->chain, st.step_id);
     }
+    return quad_ok(net, x.ss) ? &MlpSghmc::iter_quad : &MlpSghmc::iter_chunked;
+  }
+
+  // The step's tail: the last pending updates, the kinetic energies, the accept test, and the commit — in the
+  // next step's start launch, or here after the call's last step.
+  int step_accept(Step& st) {
+    const int si = st.si;
     HMCX_HIP(ctx, flush_pending(net));
     VarTab ve{};
     for (int i = 0; i < 6; ++i) {
       const int v = s->order[i];
-      ve.q[i] = cur[v]; ve.qn[i] = par[v]; ve.p[i] = pv[v]; ve.n[i] = dim[v];
+      ve.q[i] = st.cur[v]; ve.qn[i] = par[v]; ve.p[i] = pv[v]; ve.n[i] = dim[v];
     }
-    hipLaunchKernelGGL(k_sumsq12<T>, dim3(NPART, 6), dim3(256), 0, st, ve, part_new);
+    hipLaunchKernelGGL(k_sumsq12<T>, dim3(NPART, 6), dim3(256), 0, stream, ve, part_new);
     MlpAccept ac{};
     ac.part_cur = part_cur; ac.part_new = part_new; ac.lp_cur = lp_cur; ac.lp_new = lp_new;
-    ac.nlb_new = e_fr[0] ? net.nrb : net.nlb;
-    ac.nlb_cur = e_fr[1] ? net.nrb : net.nlb;
+    ac.nlb_new = st.e_fr[0] ? net.nrb : net.nlb;
+    ac.nlb_cur = st.e_fr[1] ? net.nrb : net.nlb;
     ac.B = s->B;
     for (int i = 0; i < 6; ++i) ac.dim[i] = dim[s->order[i]];
     ac.alpha = s->alpha; ac.u = s->u_accept[si];
@@ -2816,64 +2857,82 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
     ac.out_nlp = s->out_nlp ? s->out_nlp + si : nullptr;
     ac.out_E = s->out_E ? s->out_E + 2 * si : nullptr;
     ac.acc_flag = accf;
-    hipLaunchKernelGGL(k_mlp_accept, dim3(1), dim3(26 * 32), 0, st, ac);
-    if (n > 0) {                       // commit: in the next step's start launch, or here after the last step
-      if (si + 1 < s->n_steps) {
-        commit_pending = true;
-        for (int v = 0; v < 6; ++v) prev_prop[v] = cur[v];
-      } else {
-        hipLaunchKernelGGL(k_mlp_commit<T>, dim3(NPART, 6), dim3(256), 0, st, ve, accf);
-      }
+    hipLaunchKernelGGL(k_mlp_accept, dim3(1), dim3(26 * 32), 0, stream, ac);
+    if (st.n > 0 && si + 1 < s->n_steps) {
+      commit_pending = true;
+      for (int v = 0; v < 6; ++v) prev_prop[v] = st.cur[v];
+    } else if (st.n > 0) {
+      hipLaunchKernelGGL(k_mlp_commit<T>, dim3(NPART, 6), dim3(256), 0, stream, ve, accf);
     }
     HMCX_HIP(ctx, hipGetLastError());
-  }
-  if ((rc = gs.finish())) return rc;
-  if ((rc = timing_end(ctx, ctx->stream))) return rc;
-  if (net.fr_prof && net.fr_prof_n) {                        // HMCX_FWDR_PROF=<file>: append per launch
-    HMCX_HIP(ctx, hipStreamSynchronize(st));                  // {np, nrb, FR_NPH} + stamps [np][nrb][FR_NPH]
-    const size_t per = (size_t)net.nrb * FR_MAXP * FR_NPH;
-    std::vector<unsigned long long> h(per * net.fr_prof_n);
-    HMCX_HIP(ctx, hipMemcpy(h.data(), net.fr_prof, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(fr_prof_path, "ab")) {
-      for (int l = 0; l < net.fr_prof_n; ++l) {
-        const int hdr[3] = {net.fr_prof_np[l], net.nrb, FR_NPH};
-        fwrite(hdr, sizeof(int), 3, f);
-        fwrite(h.data() + l * per, sizeof(unsigned long long), (size_t)net.fr_prof_np[l] * net.nrb * FR_NPH, f);
-      }
-      fclose(f);
-    }
-  }
-  if (net.prof) {                                            // HMCX_MLP_PROF=<file>: append the stamps
-    HMCX_HIP(ctx, hipStreamSynchronize(st));
-    const size_t n = (size_t)std::min(net.l23_count, net.prof_cap) * net.nlb * ((net.n_mid + 31) / 32) * L23_NPH;
-    std::vector<unsigned long long> h(n);
-    HMCX_HIP(ctx, hipMemcpy(h.data(), net.prof, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(getenv("HMCX_MLP_PROF"), "ab")) {
-      const int hdr[4] = {std::min(net.l23_count, net.prof_cap), net.nlb, (net.n_mid + 31) / 32, L23_NPH};
-      fwrite(hdr, sizeof(int), 4, f);
-      fwrite(h.data(), sizeof(unsigned long long), n, f);
-      fclose(f);
-    }
-  }
-  if (!net.fuse) {
-    if (s->out_abort) HMCX_HIP(ctx, hipMemsetAsync(s->out_abort, 0, sizeof(int32_t), st));
     return HMCX_OK;
   }
-  // the call's verdict: the MLP abort word (raised by a timed-out exchange of any fused launch of this
-  // call) goes to out_abort and is lowered for the next call — the call's outputs and state are then
-  // invalid and the caller re-runs it unfused (sghmc._run_mlp); without out_abort, wait and report
-  if (s->out_abort) {
-    HMCX_HIP(ctx, hipMemcpyAsync(s->out_abort, ctx->mlp_abort_dev, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HMCX_HIP(ctx, hipMemsetAsync(ctx->mlp_abort_dev, 0, sizeof(int), st));
+
+  // HMCX_FWDR_PROF / HMCX_MLP_PROF=<file>: after the call, append the stamps its launches left.
+  int profiles() {
+    if (net.fr_prof && net.fr_prof_n) {                        // per k_fwdr launch {np, nrb, FR_NPH} + [np][nrb][FR_NPH]
+      const size_t per = (size_t)net.nrb * FR_MAXP * FR_NPH;
+      auto rec = [&](FILE* f, const unsigned long long* h) {
+        for (int l = 0; l < net.fr_prof_n; ++l)
+          prof_record(f, {net.fr_prof_np[l], net.nrb, FR_NPH}, h + l * per, (size_t)net.fr_prof_np[l] * net.nrb * FR_NPH);
+      };
+      if (int rc = prof_append(ctx, stream, fr_prof_path, net.fr_prof, per * net.fr_prof_n, rec)) return rc;
+    }
+    if (net.prof) {                                            // {launches, nlb, slices, L23_NPH} + their stamps
+      const int nl = std::min(net.l23_count, net.prof_cap), S = (net.n_mid + 31) / 32;
+      const size_t n = (size_t)nl * net.nlb * S * L23_NPH;
+      auto rec = [&](FILE* f, const unsigned long long* h) { prof_record(f, {nl, net.nlb, S, L23_NPH}, h, n); };
+      if (int rc = prof_append(ctx, stream, prof_path, net.prof, n, rec)) return rc;
+    }
     return HMCX_OK;
   }
-  int flag = 0;
-  HMCX_HIP(ctx, hipMemcpyAsync(&flag, ctx->mlp_abort_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-  HMCX_HIP(ctx, hipMemsetAsync(ctx->mlp_abort_dev, 0, sizeof(int), st));
-  HMCX_HIP(ctx, hipStreamSynchronize(st));
-  if (flag) return set_error(ctx, HMCX_EHIP, "mlp sghmc: fused layer-2/3 exchange timed out; state is invalid "
-                                             "(re-run with hmcx_set_mlp_fuse(ctx, 0))");
-  return HMCX_OK;
+
+  // The call's verdict: the MLP abort word (raised by a timed-out exchange of any fused launch of this call)
+  // goes to out_abort and is lowered for the next call — the call's outputs and state are then invalid and
+  // the caller re-runs it unfused (sghmc._run_mlp); without out_abort, wait and report.
+  int verdict() {
+    int32_t* out = s->out_abort;
+    if (!net.fuse) {
+      if (out) HMCX_HIP(ctx, hipMemsetAsync(out, 0, sizeof(int32_t), stream));
+      return HMCX_OK;
+    }
+    int flag = 0;
+    if (out) HMCX_HIP(ctx, hipMemcpyAsync(out, ctx->mlp_abort_dev, sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    else HMCX_HIP(ctx, hipMemcpyAsync(&flag, ctx->mlp_abort_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HMCX_HIP(ctx, hipMemsetAsync(ctx->mlp_abort_dev, 0, sizeof(int), stream));
+    if (out) return HMCX_OK;
+    HMCX_HIP(ctx, hipStreamSynchronize(stream));
+    if (flag) return set_error(ctx, HMCX_EHIP, "mlp sghmc: fused layer-2/3 exchange timed out; state is invalid "
+                                               "(re-run with hmcx_set_mlp_fuse(ctx, 0))");
+    return HMCX_OK;
+  }
+};
+}  // namespace
+
+template <typename T>
+int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
+  MlpSghmc<T> c{ctx, s};
+  Workspace ws(ctx);
+  int rc;
+  if ((rc = c.validate()) || (rc = c.plan(ws))) return rc;
+  begin_call(ctx);
+  if ((rc = timing_begin(ctx, ctx->stream))) return rc;
+  GraphScope gs(ctx);
+  c.stream = c.net.st = ctx->stream;
+  for (int si = 0; si < s->n_steps; ++si) {
+    typename MlpSghmc<T>::Step st;
+    c.step_begin(si, st);
+    c.step_start(st);
+    const auto iter = c.pick(st);                               // this step's schedule
+    for (int it = 0; it < st.n; ++it) {
+      typename MlpSghmc<T>::Iter x;
+      c.iter_begin(st, it, x);
+      if ((rc = (c.*iter)(st, x))) return rc;
+    }
+    if ((rc = st.batched ? c.energies_rest(st) : c.energies_single(st)) || (rc = c.step_accept(st))) return rc;
+  }
+  if ((rc = gs.finish()) || (rc = timing_end(ctx, ctx->stream)) || (rc = c.profiles())) return rc;
+  return c.verdict();
 }
 
 // HMCX_MLP_DTYPES (bit 0 float, bit 1 double; both by default): the build compiles this file once per
@@ -2881,23 +2940,19 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
 #ifndef HMCX_MLP_DTYPES
 #define HMCX_MLP_DTYPES 3
 #endif
+#define HMCX_MLP_INSTANTIATE(T)                                                                                       \
+  template int mlp_masks_t<T>(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);                    \
+  template int mlp_grad_t<T>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,      \
+                             const void*, double, hmcx_mlp_params*, double*);                                         \
+  template int mlp_loss_t<T>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,      \
+                             const void*, double*, void*);                                                            \
+  template int mlp_sghmc_t<T>(hmcx_ctx*, const hmcx_mlp_sghmc_args*);                                                 \
+  template int mlp_leapfrog_t<T>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
 #if HMCX_MLP_DTYPES & 1
-template int mlp_masks_t<float>(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);
-template int mlp_grad_t<float>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,
-                               const void*, double, hmcx_mlp_params*, double*);
-template int mlp_loss_t<float>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,
-                               const void*, double*, void*);
-template int mlp_sghmc_t<float>(hmcx_ctx*, const hmcx_mlp_sghmc_args*);
-template int mlp_leapfrog_t<float>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
+HMCX_MLP_INSTANTIATE(float)
 #endif
 #if HMCX_MLP_DTYPES & 2
-template int mlp_masks_t<double>(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);
-template int mlp_grad_t<double>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,
-                                const void*, double, hmcx_mlp_params*, double*);
-template int mlp_loss_t<double>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,
-                                const void*, double*, void*);
-template int mlp_sghmc_t<double>(hmcx_ctx*, const hmcx_mlp_sghmc_args*);
-template int mlp_leapfrog_t<double>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
+HMCX_MLP_INSTANTIATE(double)
 #endif
 
 }  // namespace hmcx

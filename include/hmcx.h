@@ -555,8 +555,11 @@ int hmcx_mlp_sghmc_run(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* a);
  * variable v in order[0..5]:  p_v −= ε/2·g_v;  q_v += ε·p_v;  g = grad(q);  p_v −= ε·g_v  (hmc.py:50-53),
  * then p = −p (hmc.py:55-56, as p − 2·p).  grad is hmcx_mlp_grad (∇ mean CE + ½·alpha·θ, all six
  * variables, 1 + 6·n_iter calls; every call but the last computes only the one or two components the
- * next kicks read, the last one all six); the kicks and drifts are hmcx_axpy's — the same kernels in
- * the same order as the host loop, so the trajectory is bit-identical to it.  Masks per gradient call:
+ * next kicks read, the last one all six).  The kicks and drifts between two gradient calls run in one
+ * launch of k_mlp_kicks, which mirrors k_axpy's (hmcx_axpy's) per-element arithmetic (ax = a·x; y ∓ ax),
+ * and the sign flip in k_mlp_neg6 (p − 2·p): other kernels than the host loop's, the same roundings, so
+ * the trajectory is bit-identical to it (test_hmc_mlp_device_leapfrog_equals_host_loop pins that).
+ * Masks per gradient call:
  *   HMCX_MLP_MASKS_NONE    no dropout;
  *   HMCX_MLP_MASKS_FIXED   masks [3][B][n_mid] (dtype) for every call;
  *   HMCX_MLP_MASKS_PHILOX  call k draws hmcx_mlp_masks(seed, chain, step, slot0 + k) into masks (scratch).

@@ -8,8 +8,10 @@ every one of their steps is accepted, is pinned here on every path of the sample
 * both energies of every accept test (E_current, E_new), not only A = min(1, exp(dE)), which hides
   them whenever E_new < E_current;
 * ``logp``: the nlp of the accept test's own forward of the state the epoch's last step kept;
-* k_fwdr at small shapes (waves without columns, partial row blocks, n_out from 2 to 16), with the
-  host-side forward counters (hmcx_get_mlp_forward_counts) proving which forward ran.
+* k_fwdr at small shapes (waves without columns, partial row blocks, n_out from 2 to 16);
+* which host schedule every step took (k_fwdr, quad, chunked, one at a time): the host-side forward
+  counters (hmcx_get_mlp_forward_counts) must equal, exactly, what that schedule launches for the
+  trace's path lengths (_expected_counts).
 
 Float32 energy figures (measured on an MI355X, against the float64 oracle at the float32-rounded
 inputs; worst of HMCX_MLP_FWDR=1 / 0; asserted at 4x: summation order differs between boxes):
@@ -99,8 +101,32 @@ def _expected_logp(tr):
     return [t["nlp"][0] if t["accepted"] else t["nlp"][1] for t in last]
 
 
-def _n_iters(tr):
-    return sum(int(t["L"]) - 1 for t in tr)
+def _expected_counts(tr, schedule):
+    """The forward launches (hmcx_get_mlp_forward_counts) of a run whose every step with iterations took
+    the host schedule ``schedule`` (DESIGN 5.3 "Host schedules"), from the trace's path lengths, n = L - 1
+    leapfrog iterations per step.  A step without iterations runs its two energy forwards one at a time on
+    every schedule.
+
+    * ``fwdr``: one k_fwdr launch per iteration, the energy forwards riding in the first and the last;
+    * ``quad``: two batched fused launches per iteration; both energy forwards ride along unless n = 1
+      (E_current then has no room in the only iteration's second launch and runs after it);
+    * ``chunked`` with all six fused grids co-resident (l23_fit = 6, as on the fixtures' few workgroups):
+      one batched launch per iteration and one for the two energy forwards;
+    * ``single``: six forwards per iteration and the two energy forwards, one launch each.
+
+    The formulas are derived from the host code; the library from before the host call was split into
+    per-schedule functions meets every one of them on these tests (27 of 27), so none needed correcting."""
+    ns = [int(t["L"]) - 1 for t in tr]
+    idle = 2 * sum(1 for n in ns if n == 0)
+    real = [n for n in ns if n >= 1]
+    if schedule == "fwdr":
+        return {"fwdr": sum(ns), "batched": 0, "single": idle}
+    if schedule == "quad":
+        return {"fwdr": 0, "batched": sum(2 * n + (n == 1) for n in real), "single": idle}
+    if schedule == "chunked":
+        return {"fwdr": 0, "batched": sum(n + 1 for n in real), "single": idle}
+    assert schedule == "single"
+    return {"fwdr": 0, "batched": 0, "single": sum(6 * n + 2 for n in ns)}
 
 
 # ----------------------------------------------------------------------------- float64
@@ -125,13 +151,10 @@ def test_f64_accept_reject_parity(f, variant, monkeypatch):
     for k in ref.post:
         np.testing.assert_allclose(g.post[k], ref.post[k], rtol=1e-8, atol=1e-10)
     np.testing.assert_allclose(g.logp, _expected_logp(ref.trace), rtol=1e-9, atol=0)
-    # the variant ran the forwards it names: k_fwdr is float32 only; the batched fused forwards only
-    # in the batched order
-    assert g.counts["fwdr"] == 0
-    if variant == "batched":
-        assert g.counts["batched"] > 0
-    else:
-        assert g.counts["batched"] == 0 and g.counts["single"] > 0
+    # every step ran the schedule the variant names, and no other: float64 batched is the chunked schedule
+    # (k_fwdr and quad are float32 only); HMCX_MLP_BATCH=0 and an order without W1 first run one at a time
+    print("f64 %s %s: %s" % (f.name, variant, g.counts))
+    assert g.counts == _expected_counts(ref.trace, "chunked" if variant == "batched" else "single")
 
 
 # ----------------------------------------------------------------------------- float32
@@ -156,11 +179,10 @@ def test_f32_accept_reject_parity(f, fwdr, monkeypatch):
     g = _fixture_run(f, torch.float32)
     assert [t["L"] for t in g.trace] == [t["L"] for t in ref.trace]
     assert [t["accepted"] for t in g.trace] == [t["accepted"] for t in ref.trace]
-    if f.fwdr and fwdr == "1":
-        assert g.counts["fwdr"] == _n_iters(ref.trace)            # every iteration, and nothing else
-    else:
-        assert g.counts["fwdr"] == 0
-        assert g.counts["batched"] > 0
+    # k_fwdr on every iteration and nothing else; without it (switched off, or the shape not eligible)
+    # every step on the quad schedule
+    print("f32 %s fwdr=%s: %s" % (f.name, fwdr, g.counts))
+    assert g.counts == _expected_counts(ref.trace, "fwdr" if f.fwdr and fwdr == "1" else "quad")
     for k in ref.post:
         _close(g.post[k], ref.post[k], 2e-5)
     dE_g = np.array([t["E"][0] - t["E"][1] for t in g.trace])
@@ -176,18 +198,23 @@ def test_f32_accept_reject_parity(f, fwdr, monkeypatch):
 
 
 # ----------------------------------------------------------------------------- the fallback boundary of fwdr_ok
+# the schedule each near miss lands on: all four still pass quad_ok (n_mid and n_in multiples of 4, aligned
+# masks, four fused grids co-resident)
+NEAR_MISS_SCHEDULE = {shape: "quad" for shape in fx.NEAR_MISS}
+
+
 @pytest.mark.parametrize("n_in,n_mid,n_out,B", fx.NEAR_MISS,
                          ids=["n_out17", "n_in12", "B18", "n_mid48"])
 def test_f32_near_miss_shapes_fall_back(n_in, n_mid, n_out, B):
     """One condition of fwdr_ok missed at a time, from the eligible 16-32-5 / B = 20 shape (n_out > 16,
-    n_in % 8, B % 4, n_mid % 32): one call of three steps, no k_fwdr launch, the state within 2e-5 of
-    the oracle's."""
+    n_in % 8, B % 4, n_mid % 32): one call of three steps, no k_fwdr launch but exactly the launches of
+    the schedule the shape lands on (NEAR_MISS_SCHEDULE), the state within 2e-5 of the oracle's."""
     ref = fx.oracle_run(n_in, n_mid, n_out, B, fx.NEAR_MISS_ALPHA, fx.NEAR_MISS_SEED, n_batches=3, epochs=1)
     assert min(t["L"] for t in ref.trace) >= 2                    # three real trajectories
     g = _gpu_run(n_in, n_mid, n_out, B, fx.NEAR_MISS_ALPHA, fx.NEAR_MISS_SEED, torch.float32, n_batches=3, epochs=1)
     assert [t["L"] for t in g.trace] == [t["L"] for t in ref.trace]
-    assert g.counts["fwdr"] == 0
-    assert g.counts["batched"] + g.counts["single"] > 0
+    print("f32 near miss %s: %s" % ((n_in, n_mid, n_out, B), g.counts))
+    assert g.counts == _expected_counts(ref.trace, NEAR_MISS_SCHEDULE[(n_in, n_mid, n_out, B)])
     for k in ref.post:
         _close(g.post[k], ref.post[k], 2e-5)
 
@@ -212,8 +239,12 @@ def test_philox_batched_equals_one_at_a_time_with_rejects(name, dtype, monkeypat
         monkeypatch.setenv("HMCX_MLP_BATCH", batch)
         runs.append(_gpu_run(f.n_in, f.n_mid, f.n_out, f.B, PHILOX_ALPHA, 0, dtype, philox_seed=PHILOX_SEED[name]))
     a, b = runs
-    assert a.counts["batched"] > 0 and b.counts["batched"] == 0
     assert [t["L"] for t in a.trace] == [t["L"] for t in b.trace]
+    # the schedules the two runs name (their own path lengths: no oracle follows device noise): without
+    # k_fwdr the batched float32 run is quad, the float64 run chunked
+    print("philox %s: batched %s, one at a time %s" % (name, a.counts, b.counts))
+    assert a.counts == _expected_counts(a.trace, "quad" if dtype == torch.float32 else "chunked")
+    assert b.counts == _expected_counts(b.trace, "single")
     assert [t["accepted"] for t in a.trace] == [t["accepted"] for t in b.trace]
     real = [t["accepted"] for t in a.trace if t["L"] >= 2]
     assert True in real and False in real
