@@ -148,7 +148,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query", "hmcx_p2_ahead_query",
-           "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule")
+           "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule", "hmcx_sghmc_batch_plan_query")
 
 _lib = None
 _lock = threading.Lock()
@@ -253,6 +253,8 @@ def load_library():
             lib.hmcx_p2_ahead_rule.argtypes = [c_int, c_int, c_int]
             lib.hmcx_p2_ahead_query.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int,
                                                 ctypes.POINTER(ctypes.c_longlong)]
+        if hasattr(lib, "hmcx_sghmc_batch_plan_query"):    # absent in older builds loaded for A/B runs
+            lib.hmcx_sghmc_batch_plan_query.argtypes = [c_int] * 11 + [ctypes.POINTER(ctypes.c_longlong)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
         lib.hmcx_mvn_eval.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                       c_void_p]
@@ -475,6 +477,22 @@ def philox_schedule(seed, chain0, C, step_base, path_length, eps):
     if rc != 0:
         raise HmcxError("non-finite path length (step size 0?)")
     return L, n_iter, u
+
+
+BATCH_PLAN_FIELDS = ("batched", "big", "nRB", "nDB", "fwd_rows", "fwd_waves", "fwd_tail", "fwd_nX", "nCT",
+                     "wide", "tail_last", "grad_nX")
+
+
+def sghmc_batch_plan(B, D, K, C, c_act, num_cus, tail32=-1, bfwd8=-1, tail_wg=-1, bgw_min=-1, bgw_tail=-1):
+    """Launches of one leapfrog iteration of the chain-batched SGHMC path with c_act of C chains still
+    moving, on a device of num_cus CUs (hmcx_sghmc_batch_plan_query: host arithmetic, no device).
+    Knobs left at -1 take the launcher's defaults.  Returns a dict over BATCH_PLAN_FIELDS."""
+    out = (ctypes.c_longlong * len(BATCH_PLAN_FIELDS))()
+    rc = load_library().hmcx_sghmc_batch_plan_query(B, D, K, C, c_act, num_cus, tail32, bfwd8, tail_wg, bgw_min,
+                                                    bgw_tail, out)
+    if rc != 0:
+        raise HmcxError("hmcx_sghmc_batch_plan_query: invalid arguments (%d)" % rc)
+    return dict(zip(BATCH_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def philox_uniforms_chains(seed, chains, step, slot, idx=0):

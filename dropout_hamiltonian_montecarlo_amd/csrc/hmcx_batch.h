@@ -633,6 +633,60 @@ template <typename T, int NW> struct BGW {
 };
 constexpr int BRW2 = 64;          // k_bgradw<T, 4> feature tile
 
+// Shapes the chain-batched kernels serve (the others run one k_fwd + one k_grad per iteration): at least
+// one full chain tile, the compiled class count, and an even D for the 2-element staging vectors.
+inline bool batch_path_serves(int C, int K, int D) { return C >= BCT && K == BKC && D % 2 == 0; }
+
+// Resolved measurement knobs of the chain-batched launcher (sghmc_batch_t reads them from the
+// environment; hmcx_sghmc_batch_plan_query takes them as arguments).
+struct BatchKnobs {
+  bool tail32;      // HMCX_BTAIL32: compaction-tail forwards on 32-row tiles (else the 8-wave 64-row kernel)
+  bool bfwd8;       // HMCX_BFWD8: the 8-wave kernel may serve the tail when tail32 is off
+  int tail_wg;      // HMCX_BTAIL_WG: a forward of at most this many 64-row workgroups is a tail launch
+  int bgw_min;      // HMCX_BGW_MIN: k_bgradw needs at least this many 64-feature workgroups
+  bool bgw_tail;    // HMCX_BGW_TAIL: k_bgradw dispatches a partial last feature tile last
+};
+inline BatchKnobs batch_knob_defaults(int num_cus) { return BatchKnobs{true, true, num_cus, 2 * num_cus, true}; }
+
+// The launches of one leapfrog iteration of sghmc_batch_t with c_act chains still moving (ranks <
+// c_act), and the partial-block counts of the call they share.  Host arithmetic only: the launcher
+// follows it and hmcx_sghmc_batch_plan_query reports it.
+struct BatchIterPlan {
+  bool big;                       // C >= 512: 64-row forward tiles, partials still per 32-row block
+  int nRB, nDB;                   // ll / colsum partial blocks and kin partial blocks of the call
+  int fwd_mt, fwd_waves;          // k_bfwd<T, fwd_mt, 1, fwd_waves>: 32·fwd_mt rows per tile
+  bool fwd_tail;                  // a compaction-tail launch (too few workgroups for two per CU)
+  int fwd_nX, nCT;                // row tiles × chain tiles of the forward; nCT also of the gradient
+  bool wide;                      // k_bgradw<T, 4> (64-feature tiles) instead of k_bgrad (32)
+  bool tail_last;                 // k_bgradw only: xcd_tile_tail_last dispatch
+  int grad_nX;                    // feature tiles of the gradient launch
+};
+inline BatchIterPlan plan_batch_iter(int B, int D, int C, int c_act, const BatchKnobs& k) {
+  BatchIterPlan p{};
+  p.big = C >= 512;
+  const int nX64 = (B + 63) / 64;
+  p.nRB = p.big ? 2 * nX64 : (B + 31) / 32;
+  p.nDB = (D + BRW - 1) / BRW;
+  p.nCT = (c_act + BCT - 1) / BCT;
+  p.fwd_nX = p.big ? nX64 : p.nRB;
+  // launches that leave CUs without a second workgroup: 32-row tiles (or the 8-wave 64-row kernel)
+  p.fwd_tail = p.big && p.fwd_nX * p.nCT <= k.tail_wg;
+  p.fwd_mt = p.big ? 2 : 1;
+  p.fwd_waves = 4;
+  if (p.fwd_tail && k.tail32) {
+    p.fwd_mt = 1;
+    p.fwd_nX = (B + 31) / 32;
+  } else if (p.fwd_tail && k.bfwd8) {
+    p.fwd_waves = 8;
+  }
+  // 64-feature tiles while they fill the chip's 2 workgroups per CU, 32-feature tiles after
+  const int nDB2 = (D + BRW2 - 1) / BRW2;
+  p.wide = nDB2 * p.nCT >= k.bgw_min;
+  p.grad_nX = p.wide ? nDB2 : p.nDB;
+  p.tail_last = p.wide && k.bgw_tail && nDB2 > 1 && D % BRW2 != 0 && D % BRW2 <= BRW2 / 2;
+  return p;
+}
+
 // amdgpu_waves_per_eu(2): two 4-wave workgroups per CU (the LDS allows two) need <= 256 registers.
 template <typename T, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void k_bgradw(BGradArgs<T> a) {

@@ -1621,14 +1621,21 @@ template <typename T>
 int sghmc_batch_t(hmcx_ctx* ctx, const hmcx_sampler_args* s) {
   const int B = s->B, D = s->D, K = s->K, C = s->C, N = C * K;
   // row tiles of 64 (k_bfwd<T,2>) whenever the step's first iteration has >= 32 tiles of chains;
-  // colsum/ll partials are laid out per 32-row block (a 64-row tile writes its sums and a zero block)
-  const bool big = C >= 512;
-  const int nX64 = (B + 63) / 64, nRB = big ? 2 * nX64 : (B + 31) / 32;
-  const int nDB = (D + BRW - 1) / BRW, nDB16 = (D + 15) / 16;
-  // compaction-tail launches (< one workgroup per CU at 64-row tiles): 32-row tiles, twice the workgroups
-  // (HMCX_BTAIL32=0: the 8-wave 64-row kernel, round 3)
-  const bool tail32 = !(getenv("HMCX_BTAIL32") && getenv("HMCX_BTAIL32")[0] == '0');
-  const int nDB2 = (D + BRW2 - 1) / BRW2;            // k_bgradw<T, 4> feature tiles
+  // colsum/ll partials are laid out per 32-row block (a 64-row tile writes its sums and a zero block).
+  // Which kernels an iteration launches is decided by plan_batch_iter (hmcx_batch.h) from the knobs:
+  // compaction-tail launches (< one workgroup per CU at 64-row tiles) take 32-row tiles, twice the
+  // workgroups (HMCX_BTAIL32=0, read per call: the 8-wave 64-row kernel, round 3); HMCX_BTAIL_WG /
+  // HMCX_BGW_MIN are the tile-height and feature-tile switch points (measurement knobs)
+  static const bool bf8_off = getenv("HMCX_BFWD8") && getenv("HMCX_BFWD8")[0] == '0';
+  static const int tail_wg = getenv("HMCX_BTAIL_WG") ? atoi(getenv("HMCX_BTAIL_WG")) : ctx->num_cus;
+  static const int bgw_min = getenv("HMCX_BGW_MIN") ? atoi(getenv("HMCX_BGW_MIN")) : 2 * ctx->num_cus;
+  static const bool tail_off = getenv("HMCX_BGW_TAIL") && getenv("HMCX_BGW_TAIL")[0] == '0';
+  BatchKnobs knobs{};
+  knobs.tail32 = !(getenv("HMCX_BTAIL32") && getenv("HMCX_BTAIL32")[0] == '0');
+  knobs.bfwd8 = !bf8_off; knobs.tail_wg = tail_wg; knobs.bgw_min = bgw_min; knobs.bgw_tail = !tail_off;
+  const BatchIterPlan p0 = plan_batch_iter(B, D, C, C, knobs);      // the call's layout; E_current at q0
+  const bool big = p0.big;
+  const int nRB = p0.nRB, nDB = p0.nDB, nDB16 = (D + 15) / 16;
   // dynamic LDS of the wide gradient kernel (set once per kernel)
   const size_t lds4 = BGW<T, 4>::lds();
   static bool bgw_attr = false;
@@ -1715,7 +1722,7 @@ int sghmc_batch_t(hmcx_ctx* ctx, const hmcx_sampler_args* s) {
     f.mode = FWD_LL; f.iter = -1; f.c_act = C;                      // E_current at q0 (all chains)
     f.W = (const T*)s->W; f.b = (const T*)s->b; f.pb = pb;
     f.ll_part = ll0;
-    f.nX = big ? nX64 : nRB; f.nCT = (C + BCT - 1) / BCT;
+    f.nX = big ? nRB / 2 : nRB; f.nCT = p0.nCT;
     f.nRB_all = nRB;
     if (big) hipLaunchKernelGGL((k_bfwd<T, 2, 0>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
     else hipLaunchKernelGGL((k_bfwd<T, 1, 0>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
@@ -1735,35 +1742,21 @@ int sghmc_batch_t(hmcx_ctx* ctx, const hmcx_sampler_args* s) {
     for (int it = 0; it < maxit; ++it) {
       int c_act = 0;
       while (c_act < C && ni_h[perm[(size_t)st_i * C + c_act]] > it) ++c_act;
+      const BatchIterPlan pl = plan_batch_iter(B, D, C, c_act, knobs);
       f.iter = it; f.c_act = c_act;
-      f.nX = big ? nX64 : nRB; f.nCT = (c_act + BCT - 1) / BCT;
-      // launches that leave CUs without a second workgroup: 32-row tiles (or the 8-wave 64-row kernel)
-      static const bool bf8_off = getenv("HMCX_BFWD8") && getenv("HMCX_BFWD8")[0] == '0';
-      // HMCX_BTAIL_WG / HMCX_BGW_MIN: tile-height and feature-tile switch points (measurement knobs)
-      static const int tail_wg = getenv("HMCX_BTAIL_WG") ? atoi(getenv("HMCX_BTAIL_WG")) : ctx->num_cus;
-      const bool tail = big && f.nX * f.nCT <= tail_wg;
-      if (tail && tail32) {
-        f.nX = (B + 31) / 32;
-        hipLaunchKernelGGL((k_bfwd<T, 1, 1>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
-      } else if (tail && !bf8_off)
+      f.nX = pl.fwd_nX; f.nCT = pl.nCT;
+      if (pl.fwd_waves == 8)
         hipLaunchKernelGGL((k_bfwd<T, 2, 1, 8>), dim3(xcd_grid(f.nX, f.nCT)), dim3(512), 0, st, f);
-      else if (big) hipLaunchKernelGGL((k_bfwd<T, 2, 1>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
+      else if (pl.fwd_mt == 2)
+        hipLaunchKernelGGL((k_bfwd<T, 2, 1>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
       else hipLaunchKernelGGL((k_bfwd<T, 1, 1>), dim3(xcd_grid(f.nX, f.nCT)), dim3(256), 0, st, f);
       HMCX_HIP(ctx, hipGetLastError());
       g.iter = it; g.c_act = c_act; g.slot = (uint32_t)(it + 1);
-      // 64-feature tiles while they fill the chip's 2 workgroups per CU, 32-feature tiles after
-      const int ctiles = (c_act + BCT - 1) / BCT;
-      g.nCT = ctiles;
-      static const int bgw_min = getenv("HMCX_BGW_MIN") ? atoi(getenv("HMCX_BGW_MIN")) : 2 * ctx->num_cus;
-      if (nDB2 * ctiles >= bgw_min) {
-        g.nX = nDB2;
-        static const bool tail_off = getenv("HMCX_BGW_TAIL") && getenv("HMCX_BGW_TAIL")[0] == '0';
-        g.tail_last = !tail_off && nDB2 > 1 && D % BRW2 != 0 && D % BRW2 <= BRW2 / 2;
+      g.nCT = pl.nCT; g.nX = pl.grad_nX; g.tail_last = pl.tail_last;
+      if (pl.wide)
         hipLaunchKernelGGL((k_bgradw<T, 4>), dim3(xcd_grid(g.nX, g.nCT)), dim3(256), lds4, st, g);
-      } else {
-        g.nX = nDB;
+      else
         hipLaunchKernelGGL((k_bgrad<T>), dim3(xcd_grid(g.nX, g.nCT)), dim3(256), 0, st, g);
-      }
       HMCX_HIP(ctx, hipGetLastError());
     }
     AcceptArgs<T> aa{};
@@ -1812,7 +1805,7 @@ int sghmc_run_t(hmcx_ctx* ctx, const hmcx_sampler_args* s) {
     return set_error(ctx, HMCX_EUNSUPPORTED, "persistent SGHMC needs C == 1");
   }
   static const bool no_batch = getenv("HMCX_NO_BATCH") && getenv("HMCX_NO_BATCH")[0] == '1';
-  if (C >= 16 && K == BKC && D % 2 == 0 && !no_batch) {                                // chain-batched GEMMs
+  if (batch_path_serves(C, K, D) && !no_batch) {                                       // chain-batched GEMMs
     if (s->out_mom) return set_error(ctx, HMCX_EUNSUPPORTED, "out_mom: single-chain / C < 16 paths only");
     return sghmc_batch_t<T>(ctx, s);
   }
@@ -2027,3 +2020,28 @@ template int sgld_run_t<float>(hmcx_ctx*, const hmcx_sampler_args*);
 template int sgld_run_t<double>(hmcx_ctx*, const hmcx_sampler_args*);
 
 }  // namespace hmcx
+
+// Launches of one leapfrog iteration of the chain-batched SGHMC path (plan_batch_iter, the function
+// sghmc_batch_t follows) on a device of num_cus CUs; host arithmetic only, the tests of the compaction
+// path read it.  Knobs < 0 take the launcher's defaults.  out[0..11]: chain-batched path serves the
+// shape, big, nRB, nDB, forward rows per tile, forward waves, tail forward, forward row tiles, chain
+// tiles, k_bgradw, tail_last, gradient feature tiles.
+extern "C" int hmcx_sghmc_batch_plan_query(int B, int D, int K, int C, int c_act, int num_cus, int tail32, int bfwd8,
+                                           int tail_wg, int bgw_min, int bgw_tail, long long* out) {
+  using namespace hmcx;
+  for (int i = 0; i < 12; ++i) out[i] = 0;
+  if (B < 1 || D < 1 || C < 1 || c_act < 1 || c_act > C || num_cus < 1) return HMCX_EINVAL;
+  out[0] = batch_path_serves(C, K, D);
+  if (!out[0]) return 0;
+  BatchKnobs k = batch_knob_defaults(num_cus);
+  if (tail32 >= 0) k.tail32 = tail32 != 0;
+  if (bfwd8 >= 0) k.bfwd8 = bfwd8 != 0;
+  if (tail_wg >= 0) k.tail_wg = tail_wg;
+  if (bgw_min >= 0) k.bgw_min = bgw_min;
+  if (bgw_tail >= 0) k.bgw_tail = bgw_tail != 0;
+  const BatchIterPlan p = plan_batch_iter(B, D, C, c_act, k);
+  const long long v[] = {p.big, p.nRB, p.nDB, 32 * p.fwd_mt, p.fwd_waves, p.fwd_tail, p.fwd_nX, p.nCT,
+                         p.wide, p.tail_last, p.grad_nX};
+  for (int i = 0; i < 11; ++i) out[1 + i] = v[i];
+  return 0;
+}

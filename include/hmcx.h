@@ -284,6 +284,22 @@ int hmcx_p2_plan_query(int B, int D, int K, int tsize, int num_cus, long long ld
 int hmcx_p2_ahead_query(int B, int D, int K, int tsize, int num_cus, long long lds_max, int pad, int want,
                         long long* out);
 
+/* Launches of one leapfrog iteration of the chain-batched SGHMC path (hmcx_sghmc_run with C >= 16, K = 10,
+ * even D) when c_act of the C chains are still moving, on a device of num_cus CUs (host arithmetic only, no
+ * device needed; the launcher follows the same function).  tail32, bfwd8, tail_wg, bgw_min, bgw_tail: the
+ * values of HMCX_BTAIL32, HMCX_BFWD8, HMCX_BTAIL_WG, HMCX_BGW_MIN, HMCX_BGW_TAIL, or < 0 for the defaults
+ * (1, 1, num_cus, 2·num_cus, 1).  out: host long long[12] —
+ *   [0] 1 when the chain-batched path serves the shape (else the rest is 0), [1] 64-row forward tiles at full
+ *   occupancy (C >= 512; the E_current forward always takes them then), [2] log-likelihood / column-sum
+ *   partial blocks of the call, [3] kinetic-energy partial blocks of the call,
+ *   [4] rows per forward tile (32 or 64), [5] waves per forward workgroup (4 or 8), [6] 1 when the forward is
+ *   a compaction-tail launch, [7] forward row tiles, [8] chain tiles,
+ *   [9] gradient kernel: 1 the 64-feature k_bgradw, 0 the 32-feature k_bgrad, [10] 1 when k_bgradw dispatches
+ *   its partial last feature tile last, [11] gradient feature tiles.
+ * Returns HMCX_EINVAL unless 1 <= c_act <= C and B, D, num_cus >= 1. */
+int hmcx_sghmc_batch_plan_query(int B, int D, int K, int C, int c_act, int num_cus, int tail32, int bfwd8,
+                                int tail_wg, int bgw_min, int bgw_tail, long long* out);
+
 /* Replaces hamiltonian/inference/cpu/sgld.py:31-46 (step): p = N(0,(2ε)²) − ½ε∇U; q += p.
  * With pW/pb set: hamiltonian/inference/gpu/sgld.py:11-20, p = ν⊙p_prev − ½ε∇U with
  * ν ~ N(0,(2ε)²), q += p, p written back to pW/pb. */

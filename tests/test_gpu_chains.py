@@ -68,8 +68,12 @@ def test_replica_chains_match_oracle(name, chains):
 
 
 def test_replica_chains_tail_64row_kernel_match_oracle(monkeypatch):
-    """HMCX_BTAIL32=0: the compaction-tail forwards run the 8-wave 64-row kernel instead of 32-row tiles
-    (both write the 32-row partial layout) — same oracle parity at 1024 chains."""
+    """HMCX_BTAIL32=0 selects the 8-wave 64-row kernel for compaction-tail forwards instead of 32-row
+    tiles.  In replica mode every chain has the same path length, so all 1024 chains stay active for the
+    whole trajectory (8 row tiles x 64 chain tiles = 512 workgroups, above the tail threshold of one per
+    CU) and no tail forward is launched: this checks only that the knob leaves the full-occupancy launches
+    and their oracle parity alone.  The tail forwards themselves, under both settings, are covered by
+    tests/test_gpu_chain_compaction.py."""
     monkeypatch.setenv("HMCX_BTAIL32", "0")
     test_replica_chains_match_oracle("sghmc_mnist", 1024)
 
