@@ -148,7 +148,8 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query", "hmcx_p2_ahead_query",
-           "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule", "hmcx_sghmc_batch_plan_query")
+           "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule", "hmcx_sghmc_batch_plan_query",
+           "hmcx_sghmc_ahead_stats")
 
 _lib = None
 _lock = threading.Lock()
@@ -253,6 +254,8 @@ def load_library():
             lib.hmcx_p2_ahead_rule.argtypes = [c_int, c_int, c_int]
             lib.hmcx_p2_ahead_query.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int,
                                                 ctypes.POINTER(ctypes.c_longlong)]
+        if hasattr(lib, "hmcx_sghmc_ahead_stats"):     # absent in older builds loaded for A/B runs
+            lib.hmcx_sghmc_ahead_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
         if hasattr(lib, "hmcx_sghmc_batch_plan_query"):    # absent in older builds loaded for A/B runs
             lib.hmcx_sghmc_batch_plan_query.argtypes = [c_int] * 11 + [ctypes.POINTER(ctypes.c_longlong)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
@@ -315,6 +318,15 @@ class Context:
             return
         flags = [1 if v else 0 for v in accepted]
         self.lib.hmcx_sghmc_ahead_note(self.h, (ctypes.c_int32 * len(flags))(*flags), len(flags))
+
+    def sghmc_ahead_stats(self):
+        """Look-ahead counters of the latest persistent SGHMC launch (include/hmcx.h hmcx_sghmc_ahead_stats):
+        {"redone", "stopped", "skipped"}; waits for the launch.  None when the loaded library predates them."""
+        if not hasattr(self.lib, "hmcx_sghmc_ahead_stats"):
+            return None
+        out = (ctypes.c_longlong * 3)()
+        self.check(self.lib.hmcx_sghmc_ahead_stats(self.h, out), "hmcx_sghmc_ahead_stats")
+        return {"redone": int(out[0]), "stopped": int(out[1]), "skipped": int(out[2])}
 
     def clear_abort(self):
         """Lower the context's persistent-launch abort word (include/hmcx.h hmcx_clear_abort)."""

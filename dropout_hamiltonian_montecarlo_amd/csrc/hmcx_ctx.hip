@@ -598,6 +598,7 @@ int hmcx_destroy(hmcx_ctx* ctx) {
   if (ctx->abort_dev) (void)hipFree(ctx->abort_dev);
   if (ctx->mlp_abort_dev) (void)hipFree(ctx->mlp_abort_dev);
   if (ctx->wide_abort_dev) (void)hipFree(ctx->wide_abort_dev);
+  if (ctx->ahead_stats_dev) (void)hipFree(ctx->ahead_stats_dev);
   if (ctx->zeros_dev) (void)hipFree(ctx->zeros_dev);
   if (ctx->gx_arena) (void)hipFree(ctx->gx_arena);
   if (ctx->pred_ws) (void)hipFree(ctx->pred_ws);

@@ -340,6 +340,16 @@ __device__ inline bool all_ok(bool ok, int* sh_fail) {
   return *sh_fail == 0;
 }
 
+// The same barrier with a second word read behind it: −1 when a thread failed, else sh[1] — the lane-wide
+// "leave this run" word a thread of the round wrote before the barrier (hmcx_persist2.hip, stopped runs).
+// The two LDS reads issue together, so the agreement costs no round trip of its own.
+__device__ inline int all_okq(bool ok, int* sh) {
+  if (!ok) sh[0] = 1;
+  __syncthreads();
+  const int fail = sh[0], q = sh[1];
+  return fail ? -1 : q;
+}
+
 // Deterministic workgroup sum (fixed butterfly + fixed wave order).
 __device__ inline double wsum(double v, double* sh) {
 #pragma unroll

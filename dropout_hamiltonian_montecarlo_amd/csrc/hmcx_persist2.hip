@@ -27,6 +27,8 @@
 //    carries a SECOND chain team on those G workgroups.  Lane 0 runs the even steps, lane 1 the odd ones, each
 //    assuming that the step before it rejects (≈ 91 % do at the benchmark's settings); a step whose assumption
 //    failed is run again from the true state, so every step that counts is computed exactly as without it.
+//    A run whose assumption is known to have failed is left at the next leapfrog boundary the lane agrees on
+//    (the verdict is polled once per iteration), not finished first.
 //  * The two GEMMs run on MFMA (v_mfma_f64_16x16x4 / f32_16x16x4) with operands from the LDS tile;
 //    the class dimension (KC = 10 compiled in, 16 generic) pads to the 16-wide tile.  A VALU
 //    variant with the classes in registers measured 1.7x slower (LDS-latency bound).
@@ -112,6 +114,22 @@ struct Q2Args {
   //     lane gathers XQ(k) before it redoes step k + 1, or, lane 0 at the end of the call, never rewrites).
   // The oldest unresolved step waits for nothing (V(k − 1) is published before its lane goes on), so the
   // lanes cannot wait for each other in a cycle.
+  // Stopped runs (a speculative run of step k + 1 that the lane leaves at a leapfrog boundary once V(k) =
+  // "changed" is known lane-wide; every workgroup of the lane leaves at the SAME boundary, so inside the
+  // lane the sequence of rounds only gets shorter and the arguments for XA … XS hold as they stand: across
+  // the stop the rounds run … A, D, B, [W,] | A (redo, it = −1), A, D, B …, and the D consume of the last
+  // iteration lies between the A uses of equal parity as the accept round does across a step boundary):
+  //  XV: a workgroup b that stops on the lane's flag may never have read V(k) from its own twin b'.  It no
+  //     longer needs it: the redo reads no verdict, and b' overwrites the slot with V(k + 2) only after it
+  //     read V(k + 1), which b publishes after the redo.  The slot's next poll by b is for the tag of
+  //     V(k + 2); a V(k) still in place carries T(k) and does not match.
+  //  XQ: b gathers XQ(k) by its tag T(k) whether or not it saw V(k) itself; the twin lane publishes it
+  //     unconditionally (every one of its workgroups computed the same "changed"), before its V(k), so the
+  //     gather waits for nothing that depends on b.  It still precedes the redo, whose accept round is what
+  //     the XQ argument above rests on.
+  //  A stopped run's granules stay in their slots with the run's epochs; the lane's epoch then jumps to the
+  //     value the full run would have reached, so every later round polls for an epoch larger than any the
+  //     stopped run wrote, and a slot the stopped run never reached holds an older one still.
   int oXA, oXD, oXB, oXW, oXS;
   int oXC;                                  // commit round: one granule per workgroup
   int oXAh, oXQ, oXP;
@@ -151,6 +169,8 @@ struct Q2Args {
                                             // that the step before it rejects; help is 0 then
   int laneoff;                              // lane 1's XA, XD, XB, XW and XS: lane 0's offsets plus this
   int oXV;                                  // verdict records, 8 granules (one line) per workgroup and lane
+  int* stats;                               // [8] look-ahead counters, 4 per lane (workgroup 0 of each): runs redone,
+                                            // runs stopped in flight, leapfrog iterations skipped
 };
 constexpr int P2_NINL = 32;                 // calls of up to this many steps pass their schedule inline
 // One schedule value of step s: the kernel-argument copy (inline calls) and the global array are both
@@ -681,13 +701,14 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   };
   // V(k) of the twin workgroup: one thread polls one granule with naps (a lane that waits stays off the
   // fabric); 0 / 1 = the state was kept / changed, −1 = timed out or the abort word is up
-  const auto waitV = [&](int k) -> int {
+  // `known` (thread 0's): the verdict when the run's own poll has already read it (0 / 1), else −1
+  const auto waitV = [&](int k, int known) -> int {
     if (threadIdx.x == 0) {
       const int g = (a.oXV + ((k & 1) * G + pbid) * 8) * 16;
       const unsigned tg = a.ep0 + (unsigned)k;
       unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      int res = -1;
-      for (int spins = 0;; ++spins) {
+      int res = known;
+      for (int spins = 0; known < 0; ++spins) {
         const gran_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, g, 0, 16 /* sc1 */);
         if (pass_complete(gran_miss(v, tg))) { res = decode(v) != 0.0 ? 1 : 0; break; }
         if ((spins & 63) == 63 && p2_spin_over(t0, a.abort_flag, a.oXV, tg)) break;
@@ -701,6 +722,20 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     return res;
   };
 
+  // ---- stopping a voided run in flight (look-ahead, a speculative run with leapfrogs).  Thread 0 looks for the
+  //      twin's V(s − 1) once per leapfrog iteration: one load issued at the top of the iteration and tested
+  //      behind the A publish, while the partials travel.  "Unchanged" ends the looking, and the wait after
+  //      the accept round; "changed" raises the workgroup's flag ish[3].  Every poller of the kernel takes a
+  //      missing partner for a timeout, so the lane has to leave the run as one: the flag rides in the A-AG
+  //      header's ll item, which carries nothing before the last iteration (row team: every f of one r),
+  //      and the sum of those in the B round's header (feature team: every r of one f).  Both sums run in
+  //      producer order, so after the B round of iteration i every workgroup of the lane holds the same
+  //      count of flags raised before their A-AG publish of iteration i, and all of them leave there when it
+  //      is not zero.  The item reaches no output: hdr[KC] is read as ll only in the last iteration, whose
+  //      item is the ll.  A flag raised in the last iteration travels nowhere; that run ends in the accept
+  //      round, the verdict (known by then) and the redo, as before.
+  int c_redo = 0, c_stop = 0, c_skip = 0;              // thread 0 of a lane's workgroup 0: the call's counters
+  const bool cnt0 = ah && bid == 0 && threadIdx.x == 0;
   for (int s = s_first; s < a.n_steps;) {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     const double epsd = sched_at(inl, s, a.inl[sched_k(s)].eps, a.eps);
@@ -709,6 +744,10 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     const int64_t rw = sched_at(inl, s, a.inl[sched_k(s)].row0, a.row0);
     const T* Xg = reinterpret_cast<const T*>(a.X) + (size_t)rw * D;
     const T* Yg = reinterpret_cast<const T*>(a.Y) + (size_t)rw * K;
+    const bool specrun = ah && s > 0 && !redo && n > 0;
+    int vst = -1;                                       // thread 0: V(s − 1) as this run's poll read it, −1 not yet
+    int stopj = 0;                                      // > 0: the lane left this run after that many iterations
+    if (specrun && tid == 0) { ish[1] = 0; ish[3] = 0; }   // barriers lie between this and every reader
     prof.stamp(0);
     if (s == a.force_abort && bid == G - 1) {                             // test knob: a "timed-out" member
       if (tid == 0) __hip_atomic_store(a.abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -815,8 +854,15 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       // ===== A-RS: partial logits → owners of the row slices
       prof.stamp(1);
       const int parA = (int)(uA & 1);
+      const bool vlook = specrun && tid == 0 && vst < 0;
+      gran_t vq = {0u, 0u, 0u, 0u};
+      if (vlook) vq = __builtin_amdgcn_raw_buffer_load_b128(rs, (a.oXV + (((s - 1) & 1) * G + pbid) * 8) * 16, 0, 16 /* sc1 */);
       roundA(parA);
       tstamp(s, it, 0);
+      if (vlook && pass_complete(gran_miss(vq, a.ep0 + (unsigned)(s - 1)))) {
+        vst = decode(vq) != 0.0 ? 1 : 0;
+        if (vst) ish[3] = 1;
+      }
       // B-AR: the previous iteration's bias sub-step runs here, after this workgroup's A partials went
       // out (it only has to be done before the softmax), then b' of this iteration
       if (bar && it > 0 && tid < K) {
@@ -897,8 +943,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
             for (int ii = 0; ii < nro; ++ii) c += Csr[ii * 16 + t];
             v = (double)c;
           } else if (t == KC) {
-            v = 0.0;
-            if (last) for (int ii = 0; ii < nro; ++ii) v += rowll[ii];
+            v = (specrun && ish[3]) ? 1.0 : 0.0;      // not the last iteration: the stop flag
+            if (last) { v = 0.0; for (int ii = 0; ii < nro; ++ii) v += rowll[ii]; }
           } else {
             const int m = t - HA;
             v = (double)Dme[(m / KC) * 16 + (m % KC)];
@@ -996,7 +1042,11 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
             for (int j = 0; j < 2; ++j) {
               const int i = off[j];
               if (i >= ni) continue;
-              if (i < HA) { hdr[i] = sm[j]; continue; }
+              if (i < HA) {
+                hdr[i] = sm[j];
+                if (specrun && !last && i == KC && sm[j] != 0.0) ish[1] = 1;   // flags raised in the lane
+                continue;
+              }
               const int m = i - HA, d = m / KC, k = m - (m / KC) * KC;
               if (k >= K) continue;
               const int l = d * 16 + k;
@@ -1008,9 +1058,11 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
               else if (d >= fo0 && d < fo0 + nfo) kl += (double)p * (double)p;
             }
           }
-          if (!all_ok(ok, ish)) return;
+          const int q = specrun ? all_okq(ok, ish) : all_ok(ok, ish) ? 0 : -1;
+          if (q < 0) return;
           tstamp(s, it, 5);
           prof.stamp(8);
+          if (q > 0 && !last) { stopj = it + 1; break; }
           if (last) {
             if (tid < K) {                                                    // bias sub-step, replicated
               const T gr = -((T)hdr[tid] - alpha * bpsh[tid]);
@@ -1049,6 +1101,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
         }
         tstamp(s, it, 5);
         prof.stamp(8);
+        // (both branches ended in a barrier behind the header's store)
+        if (specrun && !last && hdr[KC] != 0.0) { stopj = it + 1; break; }
         // owned weight: gradient (softmax.py:57-58), momentum (sghmc.py:31,34), drift (:32)
         if (own) {
           const T gr = -((T)sum - alpha * wv);
@@ -1100,6 +1154,19 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       }
     }
 
+    if (specrun && stopj) {                              // (specrun: the block folds away where look-ahead does)
+      // the lane left the run at a boundary: the epoch the full run would have ended on (the remaining
+      // iterations' rounds — without the B all-reduce iteration stopj − 1 had its B-AG still to come — and
+      // the accept round), then the voided run's path: the true q_s, and step s again on the tile it holds
+      // (the redo's accept round loads the next tile: pf_done is still false)
+      prof.stamp(14);
+      ep += (bar ? 3u : 4u) * (unsigned)(n - stopj) + 1u;
+      if (cnt0) { ++c_redo; ++c_stop; c_skip += n - stopj; }
+      if (!gatherQ(s - 1)) return;
+      wv = own ? Wf[wl] : T(0);
+      redo = true;
+      continue;
+    }
     if (bar && n > 0 && own) wv = Wf[wl];            // the slice lives in LDS (last write: barrier-ed)
     // ===== accept (hmc.py:67-71): all-gather of the kinetic / log-likelihood partials
     prof.stamp(10);
@@ -1164,10 +1231,11 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     if (ah && s > 0 && !redo) {
       // the twin's verdict on step s − 1 (this run assumed "state unchanged")
       prof.stamp(12);
-      const int vprev = waitV(s - 1);
+      const int vprev = waitV(s - 1, vst);
       if (vprev < 0) return;
       if (vprev) {
         prof.stamp(13);
+        if (cnt0) ++c_redo;
         if (!gatherQ(s - 1)) return;
         wv = own ? Wf[wl] : T(0);
         redo = true;
@@ -1227,6 +1295,10 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   }
   prof.stamp(0);
   prof.flush();
+  if (cnt0 && a.stats) {
+    int* st = a.stats + 4 * lanei;
+    st[0] = c_redo; st[1] = c_stop; st[2] = c_skip;
+  }
   if (ah) {
     if (lanei) {                                      // lane 1 takes no part in the commit round
       verdict.done = true;
@@ -1234,7 +1306,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     }
     // the call's last step was lane 1's: its verdict, and the final state when it moved
     if (a.n_steps >= 2 && !(a.n_steps & 1)) {
-      const int vlast = waitV(a.n_steps - 1);
+      const int vlast = waitV(a.n_steps - 1, -1);
       if (vlast < 0) return;
       if (vlast) {
         if (!gatherQ(a.n_steps - 1)) return;
@@ -1494,6 +1566,12 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   a.ahead = ahead;
   a.laneoff = (int)(lay.oL1 - lay.oXA);
   a.oXV = (int)lay.oXV;
+  if (!ctx->ahead_stats_dev) {
+    HMCX_HIP(ctx, hipMalloc((void**)&ctx->ahead_stats_dev, 8 * sizeof(int)));
+    HMCX_HIP(ctx, hipMemsetAsync(ctx->ahead_stats_dev, 0, 8 * sizeof(int), ctx->stream));
+  }
+  a.stats = ctx->ahead_stats_dev;
+  ctx->ahead_stats_on = ahead;                   // a launch without look-ahead leaves the record alone: all zero then
   a.arena_bytes = (int)(ngran * 16);
   a.ep0 = ep0;
   a.pad = pad;
@@ -1618,16 +1696,16 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
     unsigned long long hh[32];
     HMCX_HIP(ctx, hipMemcpy(hh, dprof, sizeof(hh), hipMemcpyDeviceToHost));
     (void)hipFree(dprof);
-    static const char* names[14] = {"step-start", "A-gemm+publish", "noise", "A-RS wait", "softmax", "A-AG",
+    static const char* names[15] = {"step-start", "A-gemm+publish", "noise", "A-RS wait", "softmax", "A-AG",
                                     "B-gemm+publish", "B-RS wait", "update", "B-AG", "accept", "it=-1",
-                                    "verdict wait+apply", "state gather"};
+                                    "verdict wait+apply", "state gather", "stopped run"};
     for (int ln = 0; ln < (ahead ? 2 : 1); ++ln) {
       const unsigned long long* h = hh + 16 * ln;
       unsigned long long tot = 0;
-      for (int i = 0; i < 14; ++i) tot += h[i];
+      for (int i = 0; i < 15; ++i) tot += h[i];
       fprintf(stderr, "[hmcx p2 prof] G=%dx%d Br=%d Bf=%d Ro=%d Fo=%d lane %d total %llu ticks:", pl.Gr, pl.Gf, pl.Br,
               pl.Bf, pl.Ro, pl.Fo, ln, tot);
-      for (int i = 0; i < 14; ++i) fprintf(stderr, " %s %.1f%%", names[i], tot ? 100.0 * h[i] / tot : 0.0);
+      for (int i = 0; i < 15; ++i) fprintf(stderr, " %s %.1f%% (%llu)", names[i], tot ? 100.0 * h[i] / tot : 0.0, h[i]);
       fprintf(stderr, "\n");
     }
   }
@@ -1720,6 +1798,20 @@ extern "C" int hmcx_p2_ahead_query(int B, int D, int K, int tsize, int num_cus, 
 // Fewer than P2_AHEAD_MIN steps decide nothing.  Look-ahead wins while most proposals are rejected (a
 // rejected step's successor was already running); above the break-even accept rate every accepted step
 // costs a redone one.  Two thresholds (hysteresis), derived in DESIGN §5.1 round 9.
+// The look-ahead counters of the context's latest persistent SGHMC launch (include/hmcx.h): both lanes'
+// records added, read behind the stream.
+extern "C" int hmcx_sghmc_ahead_stats(hmcx_ctx* ctx, long long out[3]) {
+  if (!ctx) return HMCX_EINVAL;
+  if (!out) return hmcx::set_error(ctx, HMCX_EINVAL, "ahead_stats: null output");
+  out[0] = out[1] = out[2] = 0;
+  if (!ctx->ahead_stats_dev || !ctx->ahead_stats_on) return HMCX_OK;
+  int h[8];
+  HMCX_HIP(ctx, hipMemcpyAsync(h, ctx->ahead_stats_dev, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  HMCX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < 3; ++i) out[i] = (long long)h[i] + h[4 + i];
+  return HMCX_OK;
+}
+
 extern "C" int hmcx_p2_ahead_rule(int on, int seen, int accepted) {
   if (seen < hmcx::P2_AHEAD_MIN) return on ? 1 : 0;
   const double rate = (double)accepted / (double)seen;

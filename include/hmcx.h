@@ -71,6 +71,11 @@ int hmcx_sghmc_ahead_note(hmcx_ctx* ctx, const int32_t* accepted /* host [n] */,
  * accept flags of the last `seen` resolved steps (at most 32), `accepted` of them set.  Fewer than 16
  * steps decide nothing; look-ahead goes off above an accept rate of 0.4 and on again below 0.3. */
 int hmcx_p2_ahead_rule(int on, int seen, int accepted);
+/* Look-ahead counters of the context's latest persistent SGHMC launch (waits for it): out[0] = speculative
+ * runs that were voided and run again, out[1] = those of them that were stopped in flight, at a leapfrog
+ * boundary, once the other lane's verdict had arrived, out[2] = leapfrog iterations so skipped.  All zero
+ * before the first launch and after a launch without look-ahead.  Timing-dependent: results never are. */
+int hmcx_sghmc_ahead_stats(hmcx_ctx* ctx, long long out[3]);
 /* Device timing of sampler runs: when enabled, HIP events on the launch stream bracket the
  * kernels of every hmcx_sghmc_run / hmcx_sgld_run call (for the persistent SGHMC path: exactly
  * its one kernel launch).  Enabling (or disabling) resets the totals; hmcx_get_timing waits
