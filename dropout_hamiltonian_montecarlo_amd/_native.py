@@ -149,7 +149,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query", "hmcx_p2_ahead_query",
            "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule", "hmcx_sghmc_batch_plan_query",
-           "hmcx_sghmc_ahead_stats")
+           "hmcx_sghmc_ahead_stats", "hmcx_sghmc_run_on_stats")
 
 _lib = None
 _lock = threading.Lock()
@@ -256,6 +256,8 @@ def load_library():
                                                 ctypes.POINTER(ctypes.c_longlong)]
         if hasattr(lib, "hmcx_sghmc_ahead_stats"):     # absent in older builds loaded for A/B runs
             lib.hmcx_sghmc_ahead_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+        if hasattr(lib, "hmcx_sghmc_run_on_stats"):    # absent in older builds loaded for A/B runs
+            lib.hmcx_sghmc_run_on_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
         if hasattr(lib, "hmcx_sghmc_batch_plan_query"):    # absent in older builds loaded for A/B runs
             lib.hmcx_sghmc_batch_plan_query.argtypes = [c_int] * 11 + [ctypes.POINTER(ctypes.c_longlong)]
         lib.hmcx_axpy.argtypes = [c_void_p, c_int, c_int, ctypes.c_int64, c_double, c_void_p, c_void_p]
@@ -327,6 +329,15 @@ class Context:
         out = (ctypes.c_longlong * 3)()
         self.check(self.lib.hmcx_sghmc_ahead_stats(self.h, out), "hmcx_sghmc_ahead_stats")
         return {"redone": int(out[0]), "stopped": int(out[1]), "skipped": int(out[2])}
+
+    def sghmc_run_on_stats(self):
+        """Parked-step counters of the latest persistent SGHMC launch (include/hmcx.h hmcx_sghmc_run_on_stats):
+        {"ran_on", "voided"}; waits for the launch.  None when the loaded library predates them."""
+        if not hasattr(self.lib, "hmcx_sghmc_run_on_stats"):
+            return None
+        out = (ctypes.c_longlong * 2)()
+        self.check(self.lib.hmcx_sghmc_run_on_stats(self.h, out), "hmcx_sghmc_run_on_stats")
+        return {"ran_on": int(out[0]), "voided": int(out[1])}
 
     def clear_abort(self):
         """Lower the context's persistent-launch abort word (include/hmcx.h hmcx_clear_abort)."""

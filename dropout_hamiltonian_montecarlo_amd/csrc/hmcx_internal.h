@@ -20,7 +20,7 @@ struct hmcx_ctx {
   int ahead_on = 1;
   uint64_t ahead_flags = 0;
   int ahead_seen = 0;
-  int* ahead_stats_dev = nullptr;      // [8] look-ahead counters of the latest launch, 4 per lane (hmcx_sghmc_ahead_stats)
+  int* ahead_stats_dev = nullptr;      // [12] look-ahead counters of the latest launch (hmcx_sghmc_ahead_stats, _run_on_stats)
   int ahead_stats_on = 0;              // the latest persistent launch ran with look-ahead and wrote them
   int num_cus = 256;
   size_t lds_max = 160 * 1024;

@@ -28,7 +28,9 @@
 //    assuming that the step before it rejects (≈ 91 % do at the benchmark's settings); a step whose assumption
 //    failed is run again from the true state, so every step that counts is computed exactly as without it.
 //    A run whose assumption is known to have failed is left at the next leapfrog boundary the lane agrees on
-//    (the verdict is polled once per iteration), not finished first.
+//    (the verdict is polled once per iteration), not finished first.  A run that ends with the verdict still
+//    unknown, and leaves the state as it was, is parked (HMCX_P2_RUNON, default on): the lane starts its next
+//    step at once and the same poll resolves the verdict while that runs.
 //  * The two GEMMs run on MFMA (v_mfma_f64_16x16x4 / f32_16x16x4) with operands from the LDS tile;
 //    the class dimension (KC = 10 compiled in, 16 generic) pads to the 16-wide tile.  A VALU
 //    variant with the classes in registers measured 1.7x slower (LDS-latency bound).
@@ -130,6 +132,34 @@ struct Q2Args {
   //  A stopped run's granules stay in their slots with the run's epochs; the lane's epoch then jumps to the
   //     value the full run would have reached, so every later round polls for an epoch larger than any the
   //     stopped run wrote, and a slot the stopped run never reached holds an older one still.
+  // Parked steps (runon: a speculative run of step p that ends with V(p − 1) unknown to the WHOLE lane and with
+  // the own decision "state unchanged" is parked — nothing published but the step's outputs — and the lane
+  // starts step p + 2 on the prefetched tile; V(p − 1) is then looked for by the poll of that run, at the latest
+  // before its accept round.  Whether the lane parks is decided from item 3 of the accept records, in which
+  // every workgroup reports what its own poll has read: the lane parks only when no workgroup has read
+  // V(p − 1), so all of them park or none does, and every workgroup of a lane is in the same run at all times):
+  //  XV, twin side: the twin overwrites the slot of V(p − 1) with V(p + 1) only after it read V(p) from THIS
+  //     workgroup, and this workgroup publishes V(p) only after it read V(p − 1) itself (in flight or in the
+  //     blocking wait), after the redo of p, or when it leaves the run of p + 2 on the lane's flag for V(p + 1) =
+  //     "changed" (next entry).  Nobody acts on another workgroup's reading of an "unchanged" verdict.
+  //  XV, stopped workgroup: the flag carries its reason.  Left on "V(p − 1) changed" (4096 per flag), a
+  //     workgroup that has not read V(p − 1) never needs it: the redo of p reads no verdict.  Left on "V(p + 1)
+  //     changed" (1 per flag), some twin published V(p + 1), which it does only after it read a V(p), and no
+  //     V(p) exists before V(p − 1) = "unchanged" is read (a "changed" one makes the whole lane redo p first): the
+  //     step p is final, the workgroup publishes V(p) = unchanged unread and never polls for T(p − 1) again.
+  //     The two reasons exclude each other within a run, so the sum of the flags tells them apart.
+  //  XQ, own side: a parked step publishes no XQ (only an unchanged state is parked; the redo publishes as ever).
+  //  XQ, twin side: XQ(p − 1) is gathered before the redo of p; the twin rewrites that parity for step p + 1
+  //     only after it read V(p), which is published after the redo.
+  //  Tile: the buffer of tile p is loaded again (tile p + 4) only in the accept round of p + 2, behind the
+  //     resolution of p.
+  //  XA … XS: the lane's sequence of rounds is that of a lane that ran p, p + 2 [, p again, p + 2 again]; a run
+  //     of p + 2 voided at its end is left behind its last B round like a stopped one, and only steps with
+  //     leapfrogs are started on a parked one, so a D consume lies between the A uses of equal parity.
+  //  Outputs: out_A … out_E of step p are written when it is parked and written again by a redo.  They are read
+  //     by the host behind the launch only; a launch that aborts is re-run as a whole.
+  //  Progress: a lane parks step p only with its step p − 2 resolved, i.e. with V(p − 2) published, so the twin's
+  //     step p − 1, the oldest unresolved step, waits for nothing, also with both lanes parked at once.
   int oXA, oXD, oXB, oXW, oXS;
   int oXC;                                  // commit round: one granule per workgroup
   int oXAh, oXQ, oXP;
@@ -169,8 +199,11 @@ struct Q2Args {
                                             // that the step before it rejects; help is 0 then
   int laneoff;                              // lane 1's XA, XD, XB, XW and XS: lane 0's offsets plus this
   int oXV;                                  // verdict records, 8 granules (one line) per workgroup and lane
-  int* stats;                               // [8] look-ahead counters, 4 per lane (workgroup 0 of each): runs redone,
-                                            // runs stopped in flight, leapfrog iterations skipped
+  int* stats;                               // [12] look-ahead counters, 4 per lane (workgroup 0 of each): runs redone,
+                                            // runs stopped in flight, leapfrog iterations skipped, steps parked;
+                                            // [8 + lane]: parked steps whose verdict came back "changed"
+  int runon;                                // 1: a lane whose verdict is pending parks the step and starts its next
+                                            // one (HMCX_P2_RUNON, default on; look-ahead launches only)
 };
 constexpr int P2_NINL = 32;                 // calls of up to this many steps pass their schedule inline
 // One schedule value of step s: the kernel-argument copy (inline calls) and the global array are both
@@ -736,6 +769,32 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   //      round, the verdict (known by then) and the redo, as before.
   int c_redo = 0, c_stop = 0, c_skip = 0;              // thread 0 of a lane's workgroup 0: the call's counters
   const bool cnt0 = ah && bid == 0 && threadIdx.x == 0;
+  // ---- parked steps (runon).  A speculative run of step p that ends with V(p − 1) unknown to the whole lane
+  //      (item 3 of the accept records: what each workgroup's poll has read) and with the own decision "state
+  //      unchanged" is parked: q restored, the outputs written, nothing published, and the lane starts step
+  //      p + 2 on the prefetched tile (pk).  The poll of that run then looks for V(p − 1) first: "unchanged"
+  //      makes p final (thread 0 publishes V(p), and goes on to look for V(p + 1)); "changed" raises the stop
+  //      flag with the reason "p is void", the lane leaves at the agreed boundary, gathers q_p, goes back to
+  //      tile p and redoes p, then runs p + 2 again.  A run of p + 2 that ends with p still parked waits for
+  //      V(p − 1) before its accept round (one pending step per lane, and tile p's buffer is the prefetch's).
+  const bool runon = ah && a.runon != 0;
+  bool pk = false;                                    // step s − 2 is parked (the same in every workgroup of the lane)
+  int pres = -1;                                      // thread 0: V(s − 3) of a parked step as read, −1 not yet
+  int c_ron = 0, c_void = 0;
+  // V(k) = unchanged, unread by anyone but the twin (thread 0)
+  const auto pubV0 = [&](int k) { put(rs, a.oXV + ((k & 1) * G + pbid) * 8, 0.0, a.ep0 + (unsigned)k); };
+  // the parked step s − 2 is void: q_{s−2}, its tile (the tile of s stays loaded in the other buffer), and again
+  const auto unpark = [&](int s_) -> bool {
+    if (!gatherQ(s_ - 3)) return false;
+    wv = own ? Wf[wl] : T(0);
+    tb ^= 1;
+    Xc = tb ? Xs2 : Xs;
+    Yc = tb ? Yo2 : Yo;
+    pf_done = true;
+    pk = false;
+    redo = true;
+    return true;
+  };
   for (int s = s_first; s < a.n_steps;) {
     const int tid = opaque((int)threadIdx.x), lane = tid & 63, wave = tid >> 6, lr = lane & 15;   // not hoisted (registers)
     const double epsd = sched_at(inl, s, a.inl[sched_k(s)].eps, a.eps);
@@ -747,6 +806,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     const bool specrun = ah && s > 0 && !redo && n > 0;
     int vst = -1;                                       // thread 0: V(s − 1) as this run's poll read it, −1 not yet
     int stopj = 0;                                      // > 0: the lane left this run after that many iterations
+    int stopk = 0;                                      // ... 1: V(s − 1) changed, 2: the parked step is void
     if (specrun && tid == 0) { ish[1] = 0; ish[3] = 0; }   // barriers lie between this and every reader
     prof.stamp(0);
     if (s == a.force_abort && bid == G - 1) {                             // test knob: a "timed-out" member
@@ -859,9 +919,18 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       if (vlook) vq = __builtin_amdgcn_raw_buffer_load_b128(rs, (a.oXV + (((s - 1) & 1) * G + pbid) * 8) * 16, 0, 16 /* sc1 */);
       roundA(parA);
       tstamp(s, it, 0);
-      if (vlook && pass_complete(gran_miss(vq, a.ep0 + (unsigned)(s - 1)))) {
-        vst = decode(vq) != 0.0 ? 1 : 0;
-        if (vst) ish[3] = 1;
+      // (a parked step's V(s − 3) comes first, in the same slot: V(s − 1) cannot be there before V(s − 2) is read)
+      const bool vpk = runon && pk && pres < 0;
+      if (vlook && pass_complete(gran_miss(vq, a.ep0 + (unsigned)(s - 1) - (vpk ? 2u : 0u)))) {
+        const int ch = decode(vq) != 0.0 ? 1 : 0;
+        if (vpk) {
+          pres = ch;
+          if (ch) ish[3] = 2;
+          else pubV0(s - 2);
+        } else {
+          vst = ch;
+          if (vst) ish[3] = 1;
+        }
       }
       // B-AR: the previous iteration's bias sub-step runs here, after this workgroup's A partials went
       // out (it only has to be done before the softmax), then b' of this iteration
@@ -943,7 +1012,9 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
             for (int ii = 0; ii < nro; ++ii) c += Csr[ii * 16 + t];
             v = (double)c;
           } else if (t == KC) {
-            v = (specrun && ish[3]) ? 1.0 : 0.0;      // not the last iteration: the stop flag
+            // not the last iteration: the stop flag, 1 for "V(s − 1) changed", 4096 for "the parked step is void"
+            // (one reason per run, at most G ≤ 256 flags: the sum tells which)
+            v = (specrun && ish[3]) ? ((runon && ish[3] == 2) ? 4096.0 : 1.0) : 0.0;
             if (last) { v = 0.0; for (int ii = 0; ii < nro; ++ii) v += rowll[ii]; }
           } else {
             const int m = t - HA;
@@ -1044,7 +1115,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
               if (i >= ni) continue;
               if (i < HA) {
                 hdr[i] = sm[j];
-                if (specrun && !last && i == KC && sm[j] != 0.0) ish[1] = 1;   // flags raised in the lane
+                if (specrun && !last && i == KC && sm[j] != 0.0) ish[1] = (runon && sm[j] >= 4096.0) ? 2 : 1;   // flags raised in the lane
                 continue;
               }
               const int m = i - HA, d = m / KC, k = m - (m / KC) * KC;
@@ -1062,7 +1133,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
           if (q < 0) return;
           tstamp(s, it, 5);
           prof.stamp(8);
-          if (q > 0 && !last) { stopj = it + 1; break; }
+          if (q > 0 && !last) { stopj = it + 1; stopk = q; break; }
           if (last) {
             if (tid < K) {                                                    // bias sub-step, replicated
               const T gr = -((T)hdr[tid] - alpha * bpsh[tid]);
@@ -1102,7 +1173,7 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
         tstamp(s, it, 5);
         prof.stamp(8);
         // (both branches ended in a barrier behind the header's store)
-        if (specrun && !last && hdr[KC] != 0.0) { stopj = it + 1; break; }
+        if (specrun && !last && hdr[KC] != 0.0) { stopj = it + 1; stopk = (runon && hdr[KC] >= 4096.0) ? 2 : 1; break; }
         // owned weight: gradient (softmax.py:57-58), momentum (sghmc.py:31,34), drift (:32)
         if (own) {
           const T gr = -((T)sum - alpha * wv);
@@ -1162,10 +1233,38 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       prof.stamp(14);
       ep += (bar ? 3u : 4u) * (unsigned)(n - stopj) + 1u;
       if (cnt0) { ++c_redo; ++c_stop; c_skip += n - stopj; }
+      if (runon && pk && stopk == 2) {                  // the parked step and this run are void
+        if (cnt0) ++c_void;
+        if (!unpark(s)) return;
+        s -= 2;
+        continue;
+      }
+      if (runon && pk) {                                // V(s − 1) exists: the parked step is final (Q2Args, XV)
+        if (tid == 0 && pres < 0) pubV0(s - 2);
+        pk = false;
+      }
       if (!gatherQ(s - 1)) return;
       wv = own ? Wf[wl] : T(0);
       redo = true;
       continue;
+    }
+    if (runon && pk) {
+      // one pending step per lane: the parked step is resolved before this run's accept round, whose prefetch
+      // loads into the parked step's tile buffer.  (Also the end of a run whose flag was raised in its last
+      // iteration and travelled nowhere.)
+      prof.stamp(12);
+      const int vp = waitV(s - 3, pres);
+      if (vp < 0) return;
+      if (vp) {
+        prof.stamp(13);
+        ++ep;                                           // this run's accept round, not held
+        if (cnt0) { ++c_redo; ++c_void; }
+        if (!unpark(s)) return;
+        s -= 2;
+        continue;
+      }
+      if (tid == 0 && pres < 0) pubV0(s - 2);
+      pk = false;
     }
     if (bar && n > 0 && own) wv = Wf[wl];            // the slice lives in LDS (last write: barrier-ed)
     // ===== accept (hmc.py:67-71): all-gather of the kinetic / log-likelihood partials
@@ -1179,6 +1278,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
       if (tid == 0) put(rs, reg + 0, kin0, ep);
       if (tid == 1) put(rs, reg + 1, kin1w, ep);
       if (tid == 2 && !hp) put(rs, reg + 2, ll0, ep);   // hp: this workgroup's helper wrote it
+      // runon, item 3: what this workgroup's poll has read of V(s − 1) — 0 nothing, 1 unchanged, 1024 changed
+      if (runon && tid == 0) put(rs, reg + 3, (s > 0 && !redo && vst >= 0) ? (vst ? 1024.0 : 1.0) : 0.0, ep);
     }
     if (hp && s + 1 < a.n_steps) xp_issue(s + 1, 0);   // p0 of the next step: tested at its start
     // next step's tile and labels while the partials travel: Xs and Yo have no reader left in this
@@ -1199,17 +1300,21 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     const int sbase = oXS + (int)(uS & 1) * G * NXS;
     ++uS;
     double v3[3] = {0.0, 0.0, 0.0};
+    double v4 = 0.0;                                    // runon: item 3 of workgroup tid's record
     if (acc1) {
-      // the three partials of workgroup tid in one batch of loads (one round trip, not three)
-      const bool ok = poll_nb<1, false, double>(rs, sbase + tid * NXS, 1, 3, -1, 0, tid < G, ep, nullptr,
-                                                a.abort_flag, stg + 3 * tid, 1);
+      // the three partials of workgroup tid in one batch of loads (one round trip, not three); runon: four
+      const int nv = runon ? 4 : 3;
+      const bool ok = poll_nb<1, false, double>(rs, sbase + tid * NXS, 1, nv, -1, 0, tid < G, ep, nullptr,
+                                                a.abort_flag, stg + nv * tid, 1);
       if (!all_ok(ok, ish)) return;
-      if (tid < G) { v3[0] = stg[3 * tid]; v3[1] = stg[3 * tid + 1]; v3[2] = stg[3 * tid + 2]; }
+      if (tid < G) { v3[0] = stg[nv * tid]; v3[1] = stg[nv * tid + 1]; v3[2] = stg[nv * tid + 2]; }
+      if (runon && tid < G) v4 = stg[nv * tid + 3];
     } else {
       bool ok = true;
 #pragma unroll
       for (int j = 0; j < 3; ++j)
         ok = ok && poll<true>(rs, sbase + j, NXS, 1, -1, tid * NXS, tid < G, ep, nullptr, 0, &v3[j], a.abort_flag);
+      if (runon) ok = ok && poll<true>(rs, sbase + 3, NXS, 1, -1, tid * NXS, tid < G, ep, nullptr, 0, &v4, a.abort_flag);
       if (!all_ok(ok, ish)) return;
     }
     const double S0 = wsum(v3[0], dsh), S1 = wsum(v3[1], dsh), L0 = wsum(v3[2], dsh);
@@ -1231,6 +1336,34 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
     if (ah && s > 0 && !redo) {
       // the twin's verdict on step s − 1 (this run assumed "state unchanged")
       prof.stamp(12);
+      if (runon) {
+        // no workgroup of the lane has read V(s − 1) (the same sum in all of them), this run leaves the state as
+        // it was, and a step with leapfrogs follows on a tile that is loaded: park the step
+        const double seen = wsum(v4, dsh);
+        const int s2 = s + 2 < a.n_steps ? s + 2 : s;
+        const int n2 = sched_at(inl, s2, a.inl[sched_k(s2)].n_iter, a.n_iter);
+        if (seen == 0.0 && (!acc || n <= 0) && s + 2 < a.n_steps && pf_done && n2 > 0) {
+          for (int e = tid; e < BfP * 16; e += QTH) Wf[e] = Wf0[e];         // keep q (sghmc.py:36-38)
+          wv = w0;
+          if (tid < 16) bsh[tid] = b0sh[tid];
+          if (bid == 0 && tid == 0) {                                       // written again if the step is redone
+            a.out_A[s] = A;
+            a.out_acc[s] = acc;
+            a.out_ll[s] = llq;
+            if (a.out_E) { a.out_E[2 * s] = Ecur; a.out_E[2 * s + 1] = Enew; }
+          }
+          if (cnt0) ++c_ron;
+          __syncthreads();
+          tb ^= 1;
+          Xc = tb ? Xs2 : Xs;
+          Yc = tb ? Yo2 : Yo;
+          pf_done = false;
+          pk = true;
+          pres = -1;
+          s += 2;
+          continue;
+        }
+      }
       const int vprev = waitV(s - 1, vst);
       if (vprev < 0) return;
       if (vprev) {
@@ -1297,7 +1430,8 @@ __global__ __launch_bounds__(QTH) void k_sghmc_p2(Q2Args a) {
   prof.flush();
   if (cnt0 && a.stats) {
     int* st = a.stats + 4 * lanei;
-    st[0] = c_redo; st[1] = c_stop; st[2] = c_skip;
+    st[0] = c_redo; st[1] = c_stop; st[2] = c_skip; st[3] = c_ron;
+    a.stats[8 + lanei] = c_void;
   }
   if (ah) {
     if (lanei) {                                      // lane 1 takes no part in the commit round
@@ -1512,8 +1646,10 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   for (size_t i = 0; i < n; ++i) rounds += 5u * (unsigned)(std::max(s->n_iter[i], 0) + 2);
   rounds += 1 + (help ? 1 : 0);                  // the commit round; with helpers E(-1), the launch's first epoch
   // look-ahead: each lane counts its own rounds from ep0 (in regions of its own) and may run each of its
-  // steps twice; the step tags ep0 + k of the verdicts lie in the same range (n_steps ≤ rounds)
-  if (ahead) rounds = 2 * rounds + 2;
+  // steps three times (as the run started on a parked step and voided with it, as a speculative run voided by
+  // its own verdict, and as the redo); the step tags ep0 + k of the verdicts lie in the same range (n_steps ≤
+  // rounds)
+  if (ahead) rounds = 3 * rounds + 2;
   unsigned ep0 = 1;
   if ((rc = gx_epochs(ctx, rounds, &ep0))) return rc;
   Q2Args a{};
@@ -1567,10 +1703,15 @@ int sghmc_p2_t(hmcx_ctx* ctx, const hmcx_sampler_args* s, const PersistPlan2& pl
   a.laneoff = (int)(lay.oL1 - lay.oXA);
   a.oXV = (int)lay.oXV;
   if (!ctx->ahead_stats_dev) {
-    HMCX_HIP(ctx, hipMalloc((void**)&ctx->ahead_stats_dev, 8 * sizeof(int)));
-    HMCX_HIP(ctx, hipMemsetAsync(ctx->ahead_stats_dev, 0, 8 * sizeof(int), ctx->stream));
+    HMCX_HIP(ctx, hipMalloc((void**)&ctx->ahead_stats_dev, 12 * sizeof(int)));
+    HMCX_HIP(ctx, hipMemsetAsync(ctx->ahead_stats_dev, 0, 12 * sizeof(int), ctx->stream));
   }
   a.stats = ctx->ahead_stats_dev;
+  // HMCX_P2_RUNON (read per call, default 1): 0 = a lane waits for the verdict at the end of every speculative run
+  {
+    const char* runon_env = getenv("HMCX_P2_RUNON");
+    a.runon = (ahead && !(runon_env && runon_env[0] == '0')) ? 1 : 0;
+  }
   ctx->ahead_stats_on = ahead;                   // a launch without look-ahead leaves the record alone: all zero then
   a.arena_bytes = (int)(ngran * 16);
   a.ep0 = ep0;
@@ -1809,6 +1950,21 @@ extern "C" int hmcx_sghmc_ahead_stats(hmcx_ctx* ctx, long long out[3]) {
   HMCX_HIP(ctx, hipMemcpyAsync(h, ctx->ahead_stats_dev, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   HMCX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 3; ++i) out[i] = (long long)h[i] + h[4 + i];
+  return HMCX_OK;
+}
+
+// The parked-step counters of the same launch (include/hmcx.h): out[0] = steps parked, out[1] = parked steps
+// whose verdict came back "changed", both lanes added.
+extern "C" int hmcx_sghmc_run_on_stats(hmcx_ctx* ctx, long long out[2]) {
+  if (!ctx) return HMCX_EINVAL;
+  if (!out) return hmcx::set_error(ctx, HMCX_EINVAL, "run_on_stats: null output");
+  out[0] = out[1] = 0;
+  if (!ctx->ahead_stats_dev || !ctx->ahead_stats_on) return HMCX_OK;
+  int h[12];
+  HMCX_HIP(ctx, hipMemcpyAsync(h, ctx->ahead_stats_dev, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  HMCX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  out[0] = (long long)h[3] + h[7];
+  out[1] = (long long)h[8] + h[9];
   return HMCX_OK;
 }
 

@@ -76,6 +76,12 @@ int hmcx_p2_ahead_rule(int on, int seen, int accepted);
  * boundary, once the other lane's verdict had arrived, out[2] = leapfrog iterations so skipped.  All zero
  * before the first launch and after a launch without look-ahead.  Timing-dependent: results never are. */
 int hmcx_sghmc_ahead_stats(hmcx_ctx* ctx, long long out[3]);
+/* Parked steps of the same launch (look-ahead; HMCX_P2_RUNON=0, read per call, turns parking off): a lane
+ * whose speculative run ends with the other lane's verdict still unknown, and leaves the state as it was,
+ * starts its next step at once and resolves the verdict while that runs.  out[0] = steps so parked, out[1] =
+ * those of them whose verdict came back "changed" (the step and the run started on it are run again).
+ * Zero and timing-dependent as above. */
+int hmcx_sghmc_run_on_stats(hmcx_ctx* ctx, long long out[2]);
 /* Device timing of sampler runs: when enabled, HIP events on the launch stream bracket the
  * kernels of every hmcx_sghmc_run / hmcx_sgld_run call (for the persistent SGHMC path: exactly
  * its one kernel launch).  Enabling (or disabling) resets the totals; hmcx_get_timing waits

@@ -15,6 +15,13 @@ Variants (`variant=`):
              lands in the last `late + 1` iterations changes nothing;
   run_on     a lane whose verdict is pending at the end of its run starts its next step at once and
              resolves the verdict only at the end of that next run.
+  run_on_poll  (`lanes_run_on_poll`, round 11) `stop` with `late`, and a lane whose run of step s ends with
+             V(s − 1) unknown and with the own decision "state unchanged" parks the step and starts step s + 2
+             at once; the poll of that run resolves V(s − 1): unchanged is seen `seen` µs after the next
+             boundary and V(s) published `seen` µs later; changed voids step s and the run, which the lane
+             leaves `late` boundaries on, gathers the state, redoes s and then runs s + 2 again.  One step
+             per lane may be parked (`pending=1`): a run that ends with the parked step unresolved waits for
+             its verdict before the accept round.
 `overhead` µs are added to every leapfrog in a lane (the price of a poll inside the iteration).
 
     python tools/p2_lane_model.py [--rate 0.092] [--steps 200000]
@@ -79,6 +86,68 @@ def lanes(n, moved, variant="parent", late=0, overhead=0.0, step=10.4, leap=7.6,
     return total / S, wait / (2.0 * total)
 
 
+def lanes_run_on_poll(n, moved, pending=1, late=1, seen=1.0, overhead=0.0, step=10.4, leap=7.6, verdict=1.5, tail=3.0,
+                      **_):
+    """µs per chain step, the share of steps parked and the share of steps parked and then voided."""
+    if pending != 1:
+        raise ValueError("one parked step per lane is all the kernel's slots allow")
+    lf = leap + overhead
+    head = step - tail
+    S = len(n)
+    dur = [step + lf * k for k in n]
+    fin = [0.0] * S
+    free = [0.0, 0.0]
+    hold = [0.0] * (S + 2)            # the accept round of the run of step s starts no earlier (a parked s − 2)
+    parked = voided = 0
+
+    def boundary(start, k, t):
+        """First boundary i of a run of k leapfrogs started at `start` that lies at or after t, or None."""
+        i = 0
+        while i < k and start + head + lf * i < t:
+            i += 1
+        return i if i < k else None
+
+    for s in range(S):
+        ln = s & 1
+        start = free[ln]
+        end = max(start + dur[s] - tail, hold[s]) + tail
+        if s == 0:
+            fin[s] = end + verdict
+            free[ln] = fin[s]
+            continue
+        vt = fin[s - 1]
+        can_park = vt > end and not moved[s] and s + 2 < S and n[s + 2] > 0
+        if can_park:
+            parked += 1
+            s2 = end                                  # the run of s + 2 starts here
+            i = boundary(s2, n[s + 2], vt)
+            if not moved[s - 1]:
+                free[ln] = s2
+                if i is not None:
+                    fin[s] = s2 + head + lf * i + 2 * seen
+                else:                                 # resolved in the blocking wait before the accept round
+                    fin[s] = max(s2 + dur[s + 2] - tail, vt) + verdict
+                    hold[s + 2] = fin[s]
+            else:
+                voided += 1
+                if i is not None and i + late <= n[s + 2] - 1:
+                    t = s2 + head + lf * (i + late)
+                else:
+                    t = max(s2 + dur[s + 2] - tail, vt)
+                fin[s] = t + 2 * verdict + dur[s]
+                free[ln] = fin[s]
+            continue
+        t = max(end, vt)
+        if moved[s - 1] and vt < end:
+            i = boundary(start, n[s], vt)
+            if i is not None and i + late <= n[s] - 1:
+                t = start + head + lf * (i + late)
+        fin[s] = t + verdict if not moved[s - 1] else t + 2 * verdict + dur[s]
+        free[ln] = fin[s]
+    total = max(fin[-1], fin[-2] if S > 1 else 0.0)
+    return total / S, parked / float(S), voided / float(S)
+
+
 def serial(n, step=7.42, leap=7.29):
     return (step * len(n) + leap * sum(n)) / len(n)
 
@@ -102,6 +171,10 @@ def main():
                      ("  ... leapfrog 0.1 us dearer", dict(variant="stop", late=1, overhead=0.1))):
         v, w = lanes(n, moved, **dict(co, **kw))
         print("%s  %.1f us per step (%+.1f %%), verdict wait %.1f %%" % (name, v, 100 * (v / base - 1), 100 * w))
+    stop1, _ = lanes(n, moved, **dict(co, variant="stop", late=1))
+    v, pk, vd = lanes_run_on_poll(n, moved, pending=1, late=1, **co)
+    print("run on, resolved by the poll  %.1f us per step (%+.1f %% on stop one boundary late), parked %.2f, voided %.3f "
+          "of the steps" % (v, 100 * (v / stop1 - 1), pk, vd))
 
 
 if __name__ == "__main__":
