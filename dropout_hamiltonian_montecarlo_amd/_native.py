@@ -84,6 +84,17 @@ class MlpPredictiveArgs(ctypes.Structure):
                 ("out_draw_correct", c_void_p)]
 
 
+class LinearPredictiveArgs(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("model", c_int), ("N", c_int), ("D", c_int), ("K", c_int),
+                ("S", c_int), ("T", c_int), ("mask_mode", c_int), ("path", c_int),
+                ("X", c_void_p), ("y", c_void_p), ("W", c_void_p), ("b", c_void_p), ("masks", c_void_p),
+                ("keep_p", c_double), ("seed", ctypes.c_uint64), ("chain", ctypes.c_uint32),
+                ("step0", ctypes.c_uint32),
+                ("out_mean", c_void_p), ("out_pred", c_void_p), ("out_entropy", c_void_p),
+                ("out_exp_entropy", c_void_p), ("out_lppd", c_void_p), ("out_draw_nll", c_void_p),
+                ("out_draw_correct", c_void_p)]
+
+
 class SgdArgs(ctypes.Structure):
     _fields_ = [("dtype", c_int), ("model", c_int), ("B", c_int), ("D", c_int), ("K", c_int), ("n_steps", c_int),
                 ("alpha", c_double), ("step_size", c_double), ("gamma", c_double),
@@ -143,7 +154,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_philox_uniforms", "hmcx_philox_normals", "hmcx_philox_normals_f64",
            "hmcx_softmax_grad", "hmcx_softmax_loglik", "hmcx_softmax_predict", "hmcx_sghmc_run",
            "hmcx_sgld_run", "hmcx_hmc_mvn_run", "hmcx_mlp_masks", "hmcx_mlp_grad", "hmcx_mlp_loss",
-           "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_predictive", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
+           "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_predictive", "hmcx_linear_predictive", "hmcx_input_masks", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
@@ -218,6 +229,9 @@ def load_library():
             lib.hmcx_mlp_hmc_leapfrog.argtypes = [c_void_p, ctypes.POINTER(MlpLeapfrogArgs)]
         if hasattr(lib, "hmcx_mlp_predictive"):
             lib.hmcx_mlp_predictive.argtypes = [c_void_p, ctypes.POINTER(MlpPredictiveArgs)]
+        if hasattr(lib, "hmcx_linear_predictive"):     # absent in older builds loaded for A/B runs
+            lib.hmcx_linear_predictive.argtypes = [c_void_p, ctypes.POINTER(LinearPredictiveArgs)]
+            lib.hmcx_input_masks.argtypes = [c_void_p, c_int, c_int, c_double, u64, u32, u32, c_void_p]
         if hasattr(lib, "hmcx_set_mlp_fuse"):          # absent in older builds loaded for A/B runs
             lib.hmcx_set_mlp_fuse.argtypes = [c_void_p, c_int]
         if hasattr(lib, "hmcx_set_sgld_fuse"):

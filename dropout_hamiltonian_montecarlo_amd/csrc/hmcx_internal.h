@@ -78,8 +78,9 @@ struct hmcx_ctx {
   int64_t recoveries[HMCX_RECOVERY_KINDS] = {0, 0, 0};
   // forward launches enqueued by hmcx_mlp_sghmc_run, by kind (hmcx_get_mlp_forward_counts)
   int64_t mlp_fwd_counts[3] = {0, 0, 0};
-  // hmcx_mlp_predictive's own buffers (logits, masks, accumulators, partials): apart from `ws`, which the
-  // per-draw forwards (mlp_loss_t) sub-allocate from offset 0 and may regrow
+  // the predictives' own buffers (hmcx_mlp_predictive, hmcx_linear_predictive: logits or probabilities, masks,
+  // accumulators, partials): apart from `ws`, which the per-draw forwards (mlp_loss_t) sub-allocate from offset 0
+  // and may regrow
   char* pred_ws = nullptr;
   size_t pred_cap = 0;
 };
@@ -265,8 +266,22 @@ template <typename T> int mlp_loss_t(hmcx_ctx*, const void*, const int32_t*, int
 template <typename T> int mlp_sghmc_t(hmcx_ctx*, const hmcx_mlp_sghmc_args*);
 template <typename T> int mlp_leapfrog_t(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
 template <typename T> int mlp_masks_t(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);
+// The predictives' own device buffer (hmcx_ctx::pred_ws, hmcx_mlp_pred.hip): grown to `bytes` (stream-
+// synchronising when it grows) and carved by Bump — two passes, the first with a null base to size it.
+int pred_reserve(hmcx_ctx* ctx, size_t bytes);
+struct Bump {
+  char* base; size_t off = 0;
+  template <typename U> U* take(size_t n) {
+    U* p = base ? reinterpret_cast<U*>(base + off) : nullptr;
+    off += (n * sizeof(U) + 255) / 256 * 256;
+    return p;
+  }
+};
 // hmcx_mlp_pred.hip: the fused path's eligibility (shape, alignment, LDS) and the call itself
 bool mlp_pred_fused_ok(const hmcx_ctx*, const hmcx_mlp_predictive_args*);
 template <typename T> int mlp_predictive_t(hmcx_ctx*, const hmcx_mlp_predictive_args*);
+// hmcx_lin_pred.hip: the same for the softmax / logistic models
+bool lin_pred_fused_ok(const hmcx_ctx*, const hmcx_linear_predictive_args*);
+template <typename T> int lin_predictive_t(hmcx_ctx*, const hmcx_linear_predictive_args*);
 
 }  // namespace hmcx

@@ -477,6 +477,22 @@ bool pred_fused_shape_ok(int n_in, int n_mid, int n_out, size_t elt, size_t lds_
 
 inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
+// draw groups of the fused launch: the fewest (≤ PF_MAXG, ≤ D) whose workgroups fill at least 90 % of the
+// rounds they occupy on `slots` resident workgroups, else the count that fills them best
+int pred_groups(int nrb, int D, int slots) {
+  int best = 1;
+  double beff = 0.0;
+  for (int G = 1; G <= std::min(D, PF_MAXG); ++G) {
+    const long long wg = (long long)nrb * G, rounds = (wg + slots - 1) / slots;
+    const double eff = (double)wg / (double)(rounds * slots);
+    if (eff >= 0.9) return G;
+    if (eff > beff) { beff = eff; best = G; }
+  }
+  return best;
+}
+
+}  // namespace
+
 // the predictive's own device buffer (see hmcx_ctx::pred_ws)
 int pred_reserve(hmcx_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->pred_cap) return HMCX_OK;
@@ -494,31 +510,6 @@ int pred_reserve(hmcx_ctx* ctx, size_t bytes) {
   ctx->pred_cap = want;
   return HMCX_OK;
 }
-struct Bump {
-  char* base; size_t off = 0;
-  template <typename U> U* take(size_t n) {
-    U* p = base ? reinterpret_cast<U*>(base + off) : nullptr;
-    off += (n * sizeof(U) + 255) / 256 * 256;
-    return p;
-  }
-};
-
-// draw groups of the fused launch: the fewest (≤ PF_MAXG, ≤ D) whose workgroups fill at least 90 % of the
-// rounds they occupy on `slots` resident workgroups, else the count that fills them best
-int pred_groups(int nrb, int D, int slots) {
-  int best = 1;
-  double beff = 0.0;
-  for (int G = 1; G <= std::min(D, PF_MAXG); ++G) {
-    const long long wg = (long long)nrb * G, rounds = (wg + slots - 1) / slots;
-    const double eff = (double)wg / (double)(rounds * slots);
-    if (eff >= 0.9) return G;
-    if (eff > beff) { beff = eff; best = G; }
-  }
-  return best;
-}
-
-}  // namespace
-
 bool mlp_pred_fused_ok(const hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   const size_t elt = a->dtype == HMCX_F64 ? 8 : 4;
   if (!pred_fused_shape_ok(a->n_in, a->n_mid, a->n_out, elt, ctx->lds_max)) return false;

@@ -25,6 +25,7 @@
 #include "hmcx_internal.h"
 #include "hmcx_persist.h"
 #include "hmcx_batch.h"
+#include "hmcx_xdrop.h"
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -851,7 +852,7 @@ __global__ void k_xdrop(const T* X, T* Xd, int64_t n, const uint8_t* keep, int m
                         uint32_t step) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool z = mode == HMCX_NOISE_BUFFER ? keep[i] != 0 : philox_uniform(seed, 0u, step, SLOT_DROPX, (uint32_t)i) < p;
+  const bool z = mode == HMCX_NOISE_BUFFER ? keep[i] != 0 : xdrop_keep(seed, 0u, step, (uint32_t)i, p);
   Xd[i] = X[i] * (z ? T(1) : T(0));                                      // np.multiply(X_batch, Z)
 }
 

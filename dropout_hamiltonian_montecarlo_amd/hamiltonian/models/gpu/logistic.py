@@ -11,7 +11,7 @@ import torch
 
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError, context, dtype_code, ptr
 
-from .softmax import _batch, as_device
+from .softmax import _PP_DOC, _batch, as_device, linear_posterior_predictive
 
 
 
@@ -127,3 +127,15 @@ class logistic:
         if prob:
             return yhat.flatten()
         return (yhat > 0.5).astype(int).flatten()
+
+    def posterior_predictive(self, posterior, X, y=None, n_dropout=0, p=0.5, Z=None, seed=0, path=0):
+        return linear_posterior_predictive(self, posterior, X, y, n_dropout, p, Z, seed, path)
+
+    posterior_predictive.__doc__ = _PP_DOC
+
+    def predict_posterior(self, posterior, X, prob=False, **kw):
+        """Posterior predictive over the parameter sets of ``posterior`` (softmax.predict_posterior's contract,
+        every row of X): the mean of P(y = 1) (prob=True) or mean > 0.5, flattened as ``predict`` returns
+        them.  Keywords go to posterior_predictive (n_dropout, p, Z, seed, path)."""
+        r = self.posterior_predictive(posterior, X, **kw)
+        return r.mean.reshape(-1) if prob else r.pred.astype(int)

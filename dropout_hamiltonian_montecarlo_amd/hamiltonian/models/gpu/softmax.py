@@ -8,10 +8,14 @@ NumPy or torch, results are torch tensors on the model's HIP device.
 Semantics follow the CPU file (the NumPy oracle): ``log_prior`` is the constant of
 softmax.py:22-30.  ``prior='gpu'`` selects the CuPy file's −½α·Σθ²/dim (gpu/softmax.py:29-39).
 """
+import ctypes
+
 import numpy as np
 import torch
 
-from dropout_hamiltonian_montecarlo_amd._native import HmcxError, context, dtype_code, ptr
+from dropout_hamiltonian_montecarlo_amd._native import (HmcxError, LinearPredictiveArgs, MLP_MASKS_FIXED, MLP_MASKS_NONE,
+                                                        MLP_MASKS_PHILOX, MODEL_LOGISTIC, MODEL_SOFTMAX, context,
+                                                        dtype_code, ptr)
 
 
 def as_device(a, dtype, device):
@@ -38,6 +42,101 @@ def _log0(x):
     its model files silence warnings, models/cpu/softmax.py:1-2)."""
     with np.errstate(divide="ignore"):
         return np.log(x)
+
+def input_masks(device, N, D, p, seed, step, chain=0):
+    """One Philox input-dropout mask [N, D] (uint8 on the device, hmcx_input_masks): what draw ``step`` of
+    posterior_predictive(n_dropout=T, p=p, seed=seed) uses, and sgd.fit_dropout's mask for that (seed, step)."""
+    ctx = context(device)
+    out = torch.empty((N, D), dtype=torch.uint8, device=ctx.device)
+    ctx.check(ctx.lib.hmcx_input_masks(ctx.h, N, D, float(p), int(seed), int(chain), int(step), ptr(out)),
+              "hmcx_input_masks")
+    return out
+
+
+def linear_posterior_predictive(model, posterior, X, y=None, n_dropout=0, p=0.5, Z=None, seed=0, path=0):
+    """posterior_predictive of the softmax and logistic models (one hmcx_linear_predictive call)."""
+    from .mlp import Predictive
+    logistic = model._hmcx_model == 'logistic'
+    Xd = model._dev(X)
+    if Xd.dim() != 2:
+        raise HmcxError("posterior_predictive: X must be [N, D]")
+    N, D = Xd.shape
+    W, b = posterior['weights'], posterior['bias']
+    W = W if isinstance(W, torch.Tensor) else np.asarray(W)
+    b = b if isinstance(b, torch.Tensor) else np.asarray(b)
+    if W.ndim < 2 or W.shape[-2] != D:
+        raise HmcxError("posterior_predictive: weights must be [..., %d, K]" % D)
+    K = int(W.shape[-1])
+    if logistic and K != 1:
+        raise HmcxError("logistic: weights must be [..., D, 1]")
+    W = model._dev(W).reshape(-1, D, K).contiguous()           # leading dimensions flatten row-major
+    S = W.shape[0]
+    b = model._dev(b).reshape(-1)
+    if b.numel() != S * K:
+        raise HmcxError("posterior_predictive: bias must be [..., %d] with the leading dimensions of weights" % K)
+    b = b.reshape(S, K).contiguous()
+    T = int(n_dropout)
+    if T < 0:
+        raise ValueError("n_dropout must be >= 0")
+    a = LinearPredictiveArgs()
+    a.dtype, a.model = model.code, MODEL_LOGISTIC if logistic else MODEL_SOFTMAX
+    a.N, a.D, a.K, a.S, a.T, a.path = N, D, K, S, max(T, 1), int(path)
+    a.X, a.W, a.b = Xd.data_ptr(), W.data_ptr(), b.data_ptr()
+    Zd = None
+    if T == 0:
+        if Z is not None:
+            raise ValueError("n_dropout=0 means no input dropout: Z must be None")
+        a.mask_mode = MLP_MASKS_NONE
+    elif Z is None:
+        a.mask_mode, a.keep_p, a.seed, a.chain, a.step0 = MLP_MASKS_PHILOX, float(p), int(seed), 0, 0
+    else:
+        Zd = Z if isinstance(Z, torch.Tensor) else torch.as_tensor(np.asarray(Z))
+        if tuple(Zd.shape) != (S * T, N, D):
+            raise HmcxError("posterior_predictive: Z must be [%d, %d, %d]" % (S * T, N, D))
+        Zd = (Zd.to(model.device) != 0).to(torch.uint8).contiguous()
+        a.mask_mode, a.masks = MLP_MASKS_FIXED, Zd.data_ptr()
+    DR = S * max(T, 1)
+    yt = None
+    if y is not None:
+        yt = y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))
+        if yt.dim() == 2 and logistic and yt.shape[1] == 1:
+            yt = yt.reshape(-1)
+        elif yt.dim() == 2 and not logistic and yt.shape[1] == K:
+            yt = yt.argmax(dim=1)                               # one-hot
+        if yt.dim() != 1 or yt.shape[0] != N:
+            raise HmcxError("posterior_predictive: y must be integer labels [N] (or one-hot [N, K])")
+        yt = yt.to(model.device, torch.int32).contiguous()
+        a.y = yt.data_ptr()
+    f64 = dict(dtype=torch.float64, device=model.device)
+    i32 = dict(dtype=torch.int32, device=model.device)
+    mean, pred = torch.empty((N, K), **f64), torch.empty(N, **i32)
+    ent, eent = torch.empty(N, **f64), torch.empty(N, **f64)
+    a.out_mean, a.out_pred = mean.data_ptr(), pred.data_ptr()
+    a.out_entropy, a.out_exp_entropy = ent.data_ptr(), eent.data_ptr()
+    lppd = nll = corr = None
+    if yt is not None:
+        lppd, nll, corr = torch.empty(N, **f64), torch.empty(DR, **f64), torch.empty(DR, **i32)
+        a.out_lppd, a.out_draw_nll, a.out_draw_correct = lppd.data_ptr(), nll.data_ptr(), corr.data_ptr()
+    ctx = context(model.device)
+    ctx.check(ctx.lib.hmcx_linear_predictive(ctx.h, ctypes.byref(a)), "hmcx_linear_predictive")
+    host = [None if t is None else t.cpu().numpy() for t in (mean, pred, ent, eent, lppd, nll, corr)]
+    del W, b, Zd, yt, Xd                                  # read by the launches the copies above waited for
+    mean, pred, ent, eent, lppd, nll, corr = host
+    return Predictive(mean, pred, ent, eent, ent - eent, lppd, nll, None if corr is None else corr / float(N))
+
+
+_PP_DOC = """Model averaging on the device in one libhmcx call (hmcx_linear_predictive): over the S parameter
+        sets of ``posterior`` ({'weights': [..., D, K], 'bias': [..., K]}: what ``sample`` returns, a
+        [chains, epochs, …] trace, or a single set; leading dimensions flatten row-major) and, with
+        ``n_dropout = T >= 1``, T Bernoulli(p) input-dropout masks per set (the reference's predict_stochastic,
+        X ⊙ Z), S·T draws in all (draw d = s·T + t); n_dropout = 0 is no input dropout.  The masks are Philox
+        draws of ``seed`` (draw d is input_masks(device, N, D, p, seed, d)) unless ``Z`` [S·T, N, D] injects them.
+        Returns mlp's ``Predictive`` of host arrays: mean [N, K] (logistic: [N, 1], the mean of P(y = 1)),
+        pred [N], entropy [N] of the mean, expected_entropy [N], mutual_information [N] and, with labels ``y``
+        ([N] class indices, or one-hot [N, K]), lppd [N], draw_nll [S·T] (−log-likelihood / N of each draw) and
+        draw_accuracy [S·T]; those three are None without y.  path: 0 by shape, 1 general, 2 fused
+        (include/hmcx.h)."""
+
 
 class softmax:
     _hmcx_model = 'softmax'
@@ -197,3 +296,8 @@ class softmax:
                                                ptr(prob_all)), "hmcx_softmax_predict")
         mean = prob_all.cpu().numpy().reshape(B, S, K).mean(axis=1)
         return mean if prob else mean.argmax(axis=1)
+
+    def posterior_predictive(self, posterior, X, y=None, n_dropout=0, p=0.5, Z=None, seed=0, path=0):
+        return linear_posterior_predictive(self, posterior, X, y, n_dropout, p, Z, seed, path)
+
+    posterior_predictive.__doc__ = _PP_DOC

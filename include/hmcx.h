@@ -653,6 +653,64 @@ typedef struct hmcx_mlp_predictive_args {
 } hmcx_mlp_predictive_args;
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a);
 
+/* Posterior predictive of the softmax and logistic models on the device (extension; the reference's
+ * predict / predict_stochastic, models/cpu/softmax.py:82-100 and logistic.py:75-87, score one parameter
+ * set and one input-dropout mask per call).  S·T draws, draw d = s·T + t: parameter set s (W [S][D][K],
+ * b [S][K], stacked as sample() returns them) under input-dropout mask t of that set,
+ *   z_d = clip((X ⊙ Z_d)·W_s + b_s)   (the clip bounds of softmax.py:40-41 / logistic.py:48-49),
+ *   softmax:  p_d = softmax(z_d), max-subtracted;   logistic (K = 1):  p_d = 1/(1 + exp(−z_d)), the class
+ *   probabilities being (1 − p_d, p_d) — S = T = 1 without masks is predict(prob=True).
+ * Masks Z_d (mask_mode, the HMCX_MLP_MASKS_* values):
+ *   NONE    no input dropout (T must be 1);
+ *   FIXED   block d of masks, uint8 [S·T][N][D] (non-zero keeps the element);
+ *   PHILOX  Z_d[n][i] = philox_uniform(seed, chain, step0 + d, 0xFFFFFFFC, n·D + i) < keep_p, the draw
+ *           hmcx_sgd_run makes for sgd.fit_dropout and hmcx_input_masks writes (an error when N·D >= 2^32
+ *           or step0 + S·T wraps 2^32).
+ * path: 0 picks by shape (the fused kernel only where it measured no slower), 1 the general path (draws in chunks: the existing forward kernel
+ * in predict mode into a chunk buffer, then a reduce launch; every shape hmcx_softmax_predict accepts),
+ * 2 the fused row-block kernel (an error when the shape is not eligible: K <= 16, and 16 rows of X plus
+ * the kernel's scratch within the 160 KiB of LDS).
+ * Outputs as hmcx_mlp_predictive's (device; each may be NULL; float64 unless noted; the softmax, sigmoid,
+ * logarithms and every sum over draws or rows in float64 and in a fixed order, so equal calls give equal
+ * bits; the general path takes p_d from the existing forward kernel, in dtype, and is float64 from there):
+ *   out_mean [N][K]          (1/(S·T)) Σ_d p_d   (logistic: the mean of p_d, [N][1])
+ *   out_pred int32 [N]       softmax: argmax_k of the mean, lowest index on ties; logistic: mean > 0.5
+ *   out_entropy [N]          entropy of the mean over the K classes (logistic: over its two), 0·log 0 = 0
+ *   out_exp_entropy [N]      (1/(S·T)) Σ_d H[p_d]
+ * and, with labels y (device int32 [N], class indices, 0/1 for logistic; asking for one of these without
+ * y is an error):
+ *   out_lppd [N]             log((1/(S·T)) Σ_d p_d[n][y_n])
+ *   out_draw_nll [S·T]       −ll_d / N, ll_d = hmcx_softmax_loglik / hmcx_logistic_loglik of X ⊙ Z_d
+ *   out_draw_correct int32 [S·T]   rows whose decision under draw d (argmax z_d; p_d > 0.5) equals y_n
+ * A NaN parameter set reaches the per-row outputs and its own draws' out_draw_nll / out_draw_correct only.
+ * Stream-ordered; returns once enqueued.  Invalid arguments return a negative code and launch nothing. */
+typedef struct hmcx_linear_predictive_args {
+  int dtype;
+  int model;               /* HMCX_MODEL_SOFTMAX or HMCX_MODEL_LOGISTIC (K = 1)           */
+  int N, D, K, S, T;
+  int mask_mode, path;
+  const void* X;           /* device [N][D] */
+  const int32_t* y;        /* device [N] or NULL */
+  const void* W;           /* device [S][D][K] */
+  const void* b;           /* device [S][K] */
+  const uint8_t* masks;    /* device [S·T][N][D], FIXED */
+  double keep_p;           /* PHILOX */
+  uint64_t seed;
+  uint32_t chain, step0;
+  double* out_mean;
+  int32_t* out_pred;
+  double* out_entropy;
+  double* out_exp_entropy;
+  double* out_lppd;
+  double* out_draw_nll;
+  int32_t* out_draw_correct;
+} hmcx_linear_predictive_args;
+int hmcx_linear_predictive(hmcx_ctx* ctx, const hmcx_linear_predictive_args* a);
+/* out[n·D + i] (device uint8 [N][D]) = the PHILOX mask of one draw: philox_uniform(seed, chain, step,
+ * 0xFFFFFFFC, n·D + i) < keep_p.  N·D must be below 2^32. */
+int hmcx_input_masks(hmcx_ctx* ctx, int N, int D, double keep_p, uint64_t seed, uint32_t chain, uint32_t step,
+                     uint8_t* out);
+
 /* on = 0: hmcx_mlp_sghmc_run stops fusing layer 2 and layer 3 into one launch (no cross-workgroup
  * exchange; one more launch per forward) — the recovery path after out_abort; on = 1 restores it. */
 int hmcx_set_mlp_fuse(hmcx_ctx* ctx, int on);
