@@ -1147,6 +1147,28 @@ int hmcx_mlp_hmc_leapfrog(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* a) {
   return a->dtype == HMCX_F64 ? mlp_leapfrog_t<double>(ctx, a) : mlp_leapfrog_t<float>(ctx, a);
 }
 
+int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
+  if (rc) return rc;
+  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgd: n_steps < 0");
+  if (!a->X || !a->y || !a->row0 || !mlp_par_ok(&a->par) || !mlp_par_ok(&a->mom))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgd: null pointer");
+  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
+      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgd: bad mask_mode");
+  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgd: FIXED masks need masks and mask_off");
+  if (a->want_eval && !a->out_eval_loss) return set_error(ctx, HMCX_EINVAL, "mlp sgd: want_eval needs out_eval_loss");
+  if (a->want_eval && a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->eval_mask_off)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgd: FIXED masks with want_eval need eval_mask_off");
+  for (int s = 0; s < a->n_steps; ++s)
+    if (a->row0[s] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgd: negative row0");
+  if (a->n_steps == 0) return HMCX_OK;
+  return a->dtype == HMCX_F64 ? mlp_sgd_t<double>(ctx, a) : mlp_sgd_t<float>(ctx, a);
+}
+
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   HMCX_GUARD_CTX(ctx);
   if (!a) return set_error(ctx, HMCX_EINVAL, "null args");

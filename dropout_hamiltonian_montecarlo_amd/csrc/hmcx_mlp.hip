@@ -1507,6 +1507,72 @@ static __global__ void k_loss_final(const double* lpart, int nlb, int B, double*
   *out = s / (double)B;
 }
 
+// One momentum-SGD step on all six variables (sgd.py:40-41; hmcx_mlp_sgd_run), grid (NPART, 6 + extra rows):
+// row v < 6, with k_mlp_init's var_blocks partition: m = γ·m − η·g, θ = θ + m (each product and sum rounded
+// once, the NumPy expression), and the block's float64 partial of Σθ² of the updated θ (part [6][NPART],
+// zeros from the idle blocks).  The rows after them hold independent work on the CUs the update leaves free, as
+// k_mlp_start's keep-flag rows do: their first workgroup finalises the step's loss from the gradient forward's
+// row-block partials (k_loss_final's arithmetic), every later one draws 256 groups of the NEXT step's dropout
+// masks (hmcx_mlp_masks's values) into the scratch the step just finished reading.
+template <typename T> struct MlpSgd {
+  VarTab vt;                          // q: θ, p: momentum, qn: the step's gradient; canonical order
+  T gamma, lr;
+  double* part;
+  const double* lpart; int nlb, B; double* out_loss;               // out_loss null: no loss
+  T* masks; int n3; uint64_t seed; uint32_t chain, step, slot;     // masks null: no draw
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_mlp_sgd(MlpSgd<T> a) {
+  if (blockIdx.y >= 6) {
+    const size_t lb = (size_t)(blockIdx.y - 6) * NPART + blockIdx.x;
+    if (lb == 0) {
+      if (a.out_loss && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int b = 0; b < a.nlb; ++b) s += a.lpart[b];
+        *a.out_loss = s / (double)a.B;
+      }
+    } else if (a.masks) {
+      const size_t g = (lb - 1) * 256 + threadIdx.x;
+      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.masks, a.n3, a.seed, a.chain, a.step, a.slot, (int)g);
+    }
+    return;
+  }
+  const int v = blockIdx.y, n = a.vt.n[v], bx = blockIdx.x;
+  const int nb = var_blocks(n);
+  if (bx >= nb) {                                              // block-uniform
+    if (threadIdx.x == 0) a.part[v * NPART + bx] = 0.0;
+    return;
+  }
+  T* q = (T*)a.vt.q[v];
+  T* p = (T*)a.vt.p[v];
+  const T* g = (const T*)a.vt.qn[v];
+  double sq = 0.0;
+  for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) {
+    const T ax = a.lr * g[i];
+    const T m = a.gamma * p[i] - ax;
+    p[i] = m;
+    const T qv = q[i] + m;
+    q[i] = qv;
+    sq += (double)qv * (double)qv;
+  }
+  block_sum2(sq, 0.0, a.part + v * NPART + bx, nullptr);
+}
+// The evaluation after a marked step: thread 0 the mean CE of the evaluation forward (k_loss_final's
+// arithmetic), threads 1..6 Σθ² of variable t − 1 from k_mlp_sgd's partials, in block order.
+static __global__ void k_mlp_sgd_eval(const double* lpart, int nlb, int B, const double* part, double* out_loss,
+                                      double* out_sumsq) {
+  const int t = threadIdx.x;
+  if (t == 0) {
+    double s = 0.0;
+    for (int b = 0; b < nlb; ++b) s += lpart[b];
+    *out_loss = s / (double)B;
+  } else if (t <= 6 && out_sumsq) {
+    double s = 0.0;
+    for (int b = 0; b < NPART; ++b) s += part[(t - 1) * NPART + b];
+    out_sumsq[t - 1] = s;
+  }
+}
+
 // ------------------------------------------------------------------ host side
 namespace {
 
@@ -2380,6 +2446,98 @@ int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
   return HMCX_OK;
 }
 
+// Momentum SGD of hmcx_mlp_sgd_run (sgd.py:36-42): per step mlp_grad_t's own launches on the step's minibatch
+// (forward, layer-1 backward, W1 / W2 gradients, the bias / W3 gradients in ONE k_pending launch — independent
+// element-wise updates, the same bits as one launch each) into a gradient workspace, then k_mlp_sgd.  With
+// n_out ≤ 32 that is 8 launches per step: layer 1, layer 2, layer 3 + CE, layer-1 backward, two weight
+// gradients, k_pending, k_mlp_sgd (n_out > 32: 9, layer 3 takes two).  A marked step adds the evaluation: its
+// masks (PHILOX: hmcx_mlp_masks's launch), mlp_loss_t's forward at the updated θ and k_mlp_sgd_eval.
+// lpart is written by the gradient forward, read by the k_mlp_sgd behind it (out_loss[s]) and only then
+// rewritten by the evaluation forward or the next step: stream order keeps the three apart.
+template <typename T>
+int mlp_sgd_t(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* s) {
+  MlpNet<T> net{};
+  Workspace ws(ctx);
+  double* lpart;
+  MaskSrc<T> ms;
+  const int B = s->B, n_mid = s->n_mid;
+  if (int rc = oneoff_net<T>(ctx, ws, net, s->X, s->y, B, s->n_in, n_mid, s->n_out, nullptr, &lpart, &ms)) return rc;
+  const bool philox = s->mask_mode == HMCX_MLP_MASKS_PHILOX, fixed = s->mask_mode == HMCX_MLP_MASKS_FIXED;
+  const int n3 = 3 * B * n_mid;
+  T *g[6], *mscr = nullptr, *escr = nullptr;
+  double* part;
+  do {                                                         // oneoff_net's takes again, then this call's own
+    ws.reset();
+    mlp_workspace<T>(ws, net);
+    lpart = ws.take<double>(net.nlb);
+    for (int v = 0; v < 6; ++v) g[v] = ws.take<T>((size_t)net.nvar(v));
+    part = ws.take<double>(6 * NPART);
+    if (philox) { mscr = ws.take<T>((size_t)n3); escr = ws.take<T>((size_t)n3); }
+  } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  if (int rc = timing_begin(ctx, ctx->stream)) return rc;
+  T* q[6];
+  MlpSgd<T> k{};
+  for (int v = 0; v < 6; ++v) {
+    q[v] = (T*)s->par.p[v];
+    k.vt.q[v] = q[v]; k.vt.p[v] = s->mom.p[v]; k.vt.qn[v] = g[v]; k.vt.n[v] = net.nvar(v);
+  }
+  k.gamma = (T)s->gamma; k.lr = (T)s->step_size;
+  k.part = part; k.lpart = lpart; k.nlb = net.nlb; k.B = B;
+  k.n3 = n3; k.seed = s->seed; k.chain = s->chain; k.slot = MASK_SLOT0;
+  const T* const X0 = (const T*)s->X;
+  // the masks of a forward: FIXED at `off` of the caller's buffer, PHILOX in `scr`, NONE nothing
+  auto masks_of = [&](const int64_t* off, int si, const T* scr) {
+    const T* m = fixed ? (const T*)s->masks + off[si] : philox ? scr : nullptr;
+    ms.vals = m;
+    net.vec_masks = n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
+  };
+  const int ng = (n3 + 63) / 64;                               // mask groups: one thread each
+  const unsigned xrows = (unsigned)(((size_t)(ng + 255) / 256 + 1 + NPART - 1) / NPART);
+  if (philox)
+    if (int rc = mlp_masks_t<T>(ctx, B, n_mid, s->seed, s->chain, s->step_base, MASK_SLOT0, mscr)) return rc;
+  int n_eval = 0;
+  for (int si = 0; si < s->n_steps; ++si) {
+    net.X = X0 + (size_t)s->row0[si] * s->n_in;
+    net.y = s->y + s->row0[si];
+    net.xw_valid = false;
+    masks_of(s->mask_off, si, mscr);
+    HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, lpart, L3Want{true, true, true, true}));
+    HMCX_HIP(ctx, mlp_ga1<T>(net, q, ms, true));
+    Upd<T> u{};
+    u.half_alpha = (T)(0.5 * s->alpha);
+    for (int v : {0, 2}) {
+      u.W = q[v]; u.G = g[v];
+      HMCX_HIP(ctx, mlp_wgrad<T>(net, q, ms, v, UPD_GRAD, u));
+    }
+    for (int v : {1, 3, 4, 5}) {
+      u.W = q[v]; u.G = g[v];
+      if (!set_pending(net, v, UPD_GRAD, u)) return pend_full(ctx);
+    }
+    HMCX_HIP(ctx, flush_pending(net));
+    const bool next_masks = philox && si + 1 < s->n_steps;
+    k.out_loss = s->out_loss ? s->out_loss + si : nullptr;
+    k.masks = next_masks ? mscr : nullptr;
+    k.step = s->step_base + (uint32_t)(si + 1);
+    const unsigned rows = next_masks ? xrows : k.out_loss ? 1u : 0u;
+    hipLaunchKernelGGL(k_mlp_sgd<T>, dim3(NPART, 6 + rows), dim3(256), 0, ctx->stream, k);
+    HMCX_HIP(ctx, hipGetLastError());
+    if (!(s->want_eval && s->want_eval[si])) continue;
+    // sgd.py:42: the state after the update on the same minibatch, fresh masks (forward 1 of the step)
+    if (philox)
+      if (int rc = mlp_masks_t<T>(ctx, B, n_mid, s->seed, s->chain, s->step_base + (uint32_t)si, MASK_SLOT0 + 1u, escr))
+        return rc;
+    masks_of(s->eval_mask_off, si, escr);
+    net.xw_valid = false;                                      // W1 moved
+    HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, lpart, L3Want{false, false, false, false}));
+    hipLaunchKernelGGL(k_mlp_sgd_eval, dim3(1), dim3(64), 0, ctx->stream, lpart, net.nlb, B, part,
+                       s->out_eval_loss + n_eval, s->out_eval_sumsq ? s->out_eval_sumsq + 6 * (size_t)n_eval : nullptr);
+    HMCX_HIP(ctx, hipGetLastError());
+    ++n_eval;
+  }
+  return timing_end(ctx, ctx->stream);
+}
+
 template <typename T>
 int mlp_loss_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, int n_mid, int n_out,
                const hmcx_mlp_params* par, const void* masks, double* loss, void* logits) {
@@ -2947,7 +3105,8 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
   template int mlp_loss_t<T>(hmcx_ctx*, const void*, const int32_t*, int, int, int, int, const hmcx_mlp_params*,      \
                              const void*, double*, void*);                                                            \
   template int mlp_sghmc_t<T>(hmcx_ctx*, const hmcx_mlp_sghmc_args*);                                                 \
-  template int mlp_leapfrog_t<T>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);
+  template int mlp_leapfrog_t<T>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);                                           \
+  template int mlp_sgd_t<T>(hmcx_ctx*, const hmcx_mlp_sgd_args*);
 #if HMCX_MLP_DTYPES & 1
 HMCX_MLP_INSTANTIATE(float)
 #endif

@@ -7,13 +7,17 @@ mask Z first (:59-63) and records −log_likelihood on the undropped last miniba
 
 One epoch is ONE libhmcx call (hmcx_sgd_run: per minibatch one k_fwd + one k_grad launch, the
 momentum update fused into the gradient epilogue); the dataset is resident in HBM for the whole
-fit.  Models: the libhmcx softmax and logistic models.
+fit.  Models: the libhmcx softmax and logistic models, and the dropout MLP (``fit`` only): there the
+WHOLE fit is one call (hmcx_mlp_sgd_run, ``_fit_mlp``) on the MLP's own dropout masks — Philox keyed
+by (seed, chain 0, global step), ``masks='off'``, or injected through ``mask_provider``; ``noise=``
+does not apply (Chainer's masks cannot be replayed).
 
 Masks of fit_dropout: ``noise='numpy'`` (default) draws Z on the host with the reference's own
 call, ``np.random.binomial(1, p, size=X_batch.shape)`` per minibatch in minibatch order, so a
 float64 fit matches the reference's up to GEMM summation order; ``noise='philox'`` draws Z on
 the device (Philox keyed by (seed, global minibatch index, element)).
 """
+import ctypes
 import sys
 
 import numpy as np
@@ -25,6 +29,8 @@ from dropout_hamiltonian_montecarlo_amd._native import HmcxError, ptr
 
 class sgd:
 
+    mask_provider = None    # MLP parity hook: f(global_step, n_forwards) -> [n_fwd, 3, B, n_mid] masks
+
     def __init__(self, model, start_p, step_size=0.1, noise='numpy', seed=0):   # sgd.py:13-16
         self.start = start_p
         self.step_size = step_size
@@ -35,8 +41,13 @@ class sgd:
         self.global_step = 0
         self.out = sys.stdout
         kind = getattr(model, '_hmcx_model', None)
+        if kind == 'mlp':
+            from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
+            if sorted(start_p.keys()) != sorted(MLP_PARAM_NAMES):
+                raise HmcxError("sgd(mlp): start_p must hold exactly %s" % (MLP_PARAM_NAMES,))
+            return
         if kind not in ('softmax', 'logistic'):
-            raise HmcxError("sgd: libhmcx implements sgd for the softmax and logistic models")
+            raise HmcxError("sgd: libhmcx implements sgd for the softmax, logistic and mlp models")
         if list(start_p.keys()) != ['weights', 'bias']:
             raise HmcxError("sgd: start_p keys must be ['weights', 'bias']")
 
@@ -104,8 +115,89 @@ class sgd:
             out[var] = par[var].detach().cpu().numpy().astype(np.float64).reshape(np.shape(self.start[var]))
         return out
 
+    # ------------------------------------------------------------------ the MLP: a whole fit in one call
+    def _fit_mlp(self, epochs, batch_size, gamma, args):
+        """gpu/sgd.py:25-47 on the dropout MLP as ONE hmcx_mlp_sgd_run: epochs·nb steps, the epoch-end
+        negative_log_posterior (sgd.py:42) evaluated on the device behind each epoch's last step.  Dropout
+        masks: ``masks='off'`` none; ``mask_provider`` set — injected (one forward per step, two on an epoch's
+        last step: gradient forward, then evaluation); else Philox keyed by (seed, chain 0, global_step)."""
+        from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
+        m = self.model
+        verbose = args.get('verbose', None)
+        B = int(batch_size)
+        Xd, yd = m._xy(args)
+        rows = list(range(0, Xd.shape[0] - B + 1, B))
+        if not rows:
+            raise ValueError("batch_size larger than the dataset: no minibatch (sgd.py:21)")
+        nb = len(rows)
+        n_steps = epochs * nb
+        row0 = np.tile(np.asarray(rows, dtype=np.int64), epochs)
+        want = np.zeros(n_steps, dtype=np.uint8)
+        want[nb - 1::nb] = 1
+        par = {k: m._dev(np.asarray(self.start[k])).clone() for k in self.start}
+        for k in par:
+            if tuple(par[k].shape) != m.shapes[k]:
+                raise HmcxError("sgd(mlp): %s has shape %s, expected %s" % (k, tuple(par[k].shape), m.shapes[k]))
+        mom = {k: torch.zeros_like(par[k]) for k in par}                  # sgd.py:35
+        dev = m.device
+        masks = args.get('masks', None)
+        if masks is not None and masks != 'off':
+            raise ValueError("masks must be None or 'off' (inject masks through mask_provider)")
+        masks_d = None
+        mask_off, eval_off = np.zeros(n_steps, dtype=np.int64), np.zeros(n_steps, dtype=np.int64)
+        if masks == 'off':
+            mode = nat.MLP_MASKS_NONE
+        elif self.mask_provider is not None:
+            mode, n3, chunks, off = nat.MLP_MASKS_FIXED, 3 * B * m.n_mid, [], 0
+            for s in range(n_steps):
+                nf = 2 if want[s] else 1
+                mk = np.asarray(self.mask_provider(self.global_step + s, nf))
+                if mk.shape != (nf, 3, B, m.n_mid):
+                    raise HmcxError("sgd(mlp): mask_provider must return [%d, 3, %d, %d]" % (nf, B, m.n_mid))
+                chunks.append(mk.reshape(-1))
+                mask_off[s], eval_off[s] = off, off + n3
+                off += nf * n3
+            if chunks:
+                masks_d = torch.from_numpy(np.concatenate(chunks)).to(dev, m.dtype)
+        else:
+            mode = nat.MLP_MASKS_PHILOX
+        f64 = dict(dtype=torch.float64, device=dev)
+        out_loss = torch.empty(n_steps, **f64)
+        ev_loss, ev_ss = torch.empty(epochs, **f64), torch.empty((epochs, 6), **f64)
+        a = nat.MlpSgdArgs()
+        a.dtype = m.code
+        a.B, a.n_in, a.n_mid, a.n_out, a.n_steps = B, m.n_in, m.n_mid, m.n_out, n_steps
+        a.alpha, a.step_size, a.gamma = m.alpha, float(self.step_size), float(gamma)
+        a.X, a.y = ptr(Xd), ptr(yd)
+        a.row0 = row0.ctypes.data_as(nat.c_i64p)
+        a.want_eval = want.ctypes.data_as(nat.c_u8p)
+        a.mask_mode, a.masks = mode, ptr(masks_d)
+        a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
+        a.eval_mask_off = eval_off.ctypes.data_as(nat.c_i64p)
+        a.seed, a.chain, a.step_base = self.seed, 0, self.global_step & 0xFFFFFFFF
+        for i, k in enumerate(MLP_PARAM_NAMES):
+            a.par.p[i], a.mom.p[i] = par[k].data_ptr(), mom[k].data_ptr()
+        a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
+        ctx = nat.context(dev)
+        if n_steps:
+            ctx.check(ctx.lib.hmcx_mlp_sgd_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgd_run")
+        self.global_step += n_steps
+        self.loss_trace = out_loss.cpu().numpy()                          # waits for the call
+        el, ss = ev_loss.cpu().numpy(), ev_ss.cpu().numpy()
+        del masks_d, Xd, yd
+        loss_val = np.zeros(epochs)
+        for i in range(epochs):
+            parts = [el[i]] + [ss[i, MLP_PARAM_NAMES.index(k)] for k in self.start]
+            loss_val[i] = m.nlp_from_parts(parts, self.start)
+            if verbose and (i % (epochs / 10) == 0):
+                print('loss: {0:.4f}'.format(loss_val[i]), file=self.out)
+        self.last_state, self.last_momentum = par, mom
+        return self._host(par), loss_val
+
     # ------------------------------------------------------------------ reference surface
     def fit(self, epochs=1, batch_size=1, gamma=0.9, **args):            # sgd.py:25-45
+        if self.model._hmcx_model == 'mlp':
+            return self._fit_mlp(int(epochs), batch_size, gamma, args)
         verbose = args.get('verbose', None)
         epochs = int(epochs)
         loss_val = np.zeros(epochs)
@@ -120,6 +212,9 @@ class sgd:
         return self._host(par), loss_val
 
     def fit_dropout(self, epochs=1, batch_size=1, gamma=0.9, p=0.5, **args):   # sgd.py:47-70
+        if self.model._hmcx_model == 'mlp':
+            raise HmcxError("sgd.fit_dropout: not implemented for the mlp model (its own dropout layers are "
+                            "what fit trains with; input-Bernoulli masks on top are not built)")
         verbose = args.get('verbose', None)
         epochs = int(epochs)
         loss_val = np.zeros(epochs)

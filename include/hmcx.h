@@ -609,6 +609,49 @@ typedef struct hmcx_mlp_leapfrog_args {
 } hmcx_mlp_leapfrog_args;
 int hmcx_mlp_hmc_leapfrog(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* a);
 
+/* Momentum SGD on the MLP, a whole fit in one call: replaces the loop of hamiltonian/inference/gpu/sgd.py:25-47
+ * (cpu/sgd.py:36-42) over models/gpu/mlp.py:47-64.  Per step s on the minibatch rows row0[s] .. row0[s] + B:
+ *   g = grad(θ) — the values hmcx_mlp_grad returns for the step's masks (∇ mean CE + ½·alpha·θ), then for every
+ *   element of all six variables  m = gamma·m − step_size·g;  θ = θ + m  (sgd.py:40-41), in dtype.
+ * out_loss[s] is the mean CE of that gradient forward (θ before the update).  Where want_eval[s] is set the
+ * state after the update is evaluated on the same minibatch under fresh masks (sgd.py:42): the e-th set flag
+ * (step order, n_evals flags in all) writes out_eval_loss[e] = the mean CE (hmcx_mlp_loss's value) and
+ * out_eval_sumsq[e][v] = Σθ² (float64, fixed summation order) of canonical variable v (0=W1 .. 5=b3) — the
+ * pieces of negative_log_posterior (mlp.py:80-82), which the caller composes in its own variable order.
+ * Masks (the HMCX_MLP_MASKS_* values):
+ *   NONE    no dropout;
+ *   FIXED   the gradient forward of step s reads masks + mask_off[s], the evaluation after it
+ *           masks + eval_mask_off[s] (3·B·n_mid values each, dtype);
+ *   PHILOX  the gradient forward of step s uses what hmcx_mlp_masks(ctx, dtype, B, n_mid, seed, chain,
+ *           step_base + s, 0x80000000, ·) writes, the evaluation after it slot 0x80000001 (SGHMC's
+ *           "slot 0x80000000 + f", f the forward index within the step).
+ * One call of n steps equals any split into calls that carry par / mom and advance step_base, bit for bit.
+ * Every launch is the unfused one of hmcx_mlp_grad / hmcx_mlp_loss (no cross-workgroup exchange, nothing
+ * that could time out: no out_abort), plus one element-wise launch per step (k_mlp_sgd: the update, the next
+ * step's Philox masks, the Σθ² partials and the step's loss).  n_steps == 0 does nothing.  Stream-ordered;
+ * returns once enqueued. */
+typedef struct hmcx_mlp_sgd_args {
+  int dtype;
+  int B, n_in, n_mid, n_out, n_steps;
+  double alpha, step_size, gamma;
+  const void* X;              /* device [N][n_in] */
+  const int32_t* y;           /* device [N] labels */
+  const int64_t* row0;        /* host [n_steps]: minibatch of step s = rows row0[s] .. +B */
+  const uint8_t* want_eval;   /* host [n_steps] or NULL: 1 = evaluate after step s */
+  int mask_mode;              /* HMCX_MLP_MASKS_NONE / _FIXED / _PHILOX */
+  const void* masks;          /* device (dtype), FIXED */
+  const int64_t* mask_off;    /* host [n_steps], FIXED: masks of step s's gradient forward */
+  const int64_t* eval_mask_off;/* host [n_steps], FIXED: masks of the evaluation after step s (read where want_eval) */
+  uint64_t seed;
+  uint32_t chain, step_base;
+  hmcx_mlp_params par;        /* state, updated in place */
+  hmcx_mlp_params mom;        /* momentum, updated in place (zeros at fit start, sgd.py:35) */
+  double* out_loss;           /* device [n_steps] or NULL */
+  double* out_eval_loss;      /* device [n_evals] */
+  double* out_eval_sumsq;     /* device [n_evals][6] */
+} hmcx_mlp_sgd_args;
+int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a);
+
 /* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
  * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
  * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
