@@ -1573,6 +1573,93 @@ static __global__ void k_mlp_sgd_eval(const double* lpart, int nlb, int B, const
   }
 }
 
+// One SGLD step on all six variables (cpu/sgld.py:31-46, gpu/sgld.py:11-26; hmcx_mlp_sgld_run), grid
+// (NPART, 6 + extra rows) laid out as k_mlp_sgd's: row v < 6 (canonical variable v, var_blocks partition)
+// draws or reads the element's standard normal z and applies the variant's update, every product and sum
+// rounded once in T:
+//   variant 0:  p = (2ε)·z;  p = p + (−½ε)·g;  θ = θ + p
+//   variant 1:  p = ((2ε)·z)·p_prev − (½ε)·g;  θ = θ + p;  p stored
+// then stores θ into the step's draw slot (vt.qc[v], null: not a kept step) and writes the block's float64
+// partial of Σθ² (part [6][NPART], zeros from the idle blocks).  The noise is indexed by e = e0[v] + i, the
+// variable's offset in the caller's order plus the index.  A thread takes whole Philox blocks — the four
+// consecutive e of one float block (philox_normal4), the two of one double block (philox_pair_d): one Philox
+// call per block, the values philox_normal_t<T> gives each e — so a variable's first and last block may be
+// shared with its neighbours in the layout: the elements outside [0, n) are skipped.  BUFFER noise walks the
+// same groups.  The spare rows are k_mlp_sgd's: the step's loss and the NEXT step's dropout masks.
+__device__ inline void sgld_normals(uint64_t seed, uint32_t chain, uint32_t step, uint32_t blk, float (&z)[4]) {
+  philox_normal4(seed, chain, step, 0u, blk, z);
+}
+__device__ inline void sgld_normals(uint64_t seed, uint32_t chain, uint32_t step, uint32_t blk, double (&z)[2]) {
+  philox_pair_d(seed, chain, step, 0u, blk, z[0], z[1]);
+}
+template <typename T> struct MlpSgld {
+  VarTab vt;                          // q: θ, p: momentum (variant 1), qn: gradient, qc: draw slot; canonical order
+  T two_eps, half_eps;                // (T)(2ε); variant 0: (T)(−½ε), variant 1: (T)(½ε)
+  int variant, noise_mode;
+  const double* noise;                // BUFFER: the step's P normals
+  uint64_t seed; uint32_t chain, step;
+  double* part;
+  const double* lpart; int nlb, B; double* out_loss;               // out_loss null: no loss
+  T* masks; int n3; uint32_t mstep, slot;                          // masks null: no draw
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_mlp_sgld(MlpSgld<T> a) {
+  if (blockIdx.y >= 6) {
+    const size_t lb = (size_t)(blockIdx.y - 6) * NPART + blockIdx.x;
+    if (lb == 0) {
+      if (a.out_loss && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int b = 0; b < a.nlb; ++b) s += a.lpart[b];
+        *a.out_loss = s / (double)a.B;
+      }
+    } else if (a.masks) {
+      const size_t g = (lb - 1) * 256 + threadIdx.x;
+      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.masks, a.n3, a.seed, a.chain, a.mstep, a.slot, (int)g);
+    }
+    return;
+  }
+  const int v = blockIdx.y, n = a.vt.n[v], bx = blockIdx.x;
+  const int nb = var_blocks(n);
+  if (bx >= nb) {                                              // block-uniform
+    if (threadIdx.x == 0) a.part[v * NPART + bx] = 0.0;
+    return;
+  }
+  T* q = (T*)a.vt.q[v];
+  T* p = (T*)a.vt.p[v];
+  T* draw = (T*)a.vt.qc[v];
+  const T* g = (const T*)a.vt.qn[v];
+  const int e0 = a.vt.e0[v];                                   // e0 + n ≤ P < 2^31 (the host's int offsets)
+  constexpr int G = sizeof(T) == 4 ? 4 : 2;                    // normals per Philox block
+  const int blk0 = e0 / G, nblk = (int)(((int64_t)e0 + n + G - 1) / G) - blk0;   // blocks holding an element of v
+  const bool philox = a.noise_mode == HMCX_NOISE_PHILOX;
+  double sq = 0.0;
+  for (int b = bx * 256 + (int)threadIdx.x; b < nblk; b += nb * 256) {
+    T z[G] = {};
+    if (philox) sgld_normals(a.seed, a.chain, a.step, (uint32_t)(blk0 + b), z);
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int64_t e = G * (int64_t)(blk0 + b) + j, i = e - e0;
+      if (i < 0 || i >= n) continue;
+      const T zi = philox ? z[j] : (T)a.noise[e];
+      const T nu = a.two_eps * zi;
+      const T hg = a.half_eps * g[i];
+      T m;
+      if (a.variant == 0) {
+        m = nu + hg;
+      } else {
+        const T np = nu * p[i];
+        m = np - hg;
+        p[i] = m;
+      }
+      const T qv = q[i] + m;
+      q[i] = qv;
+      if (draw) draw[i] = qv;
+      sq += (double)qv * (double)qv;
+    }
+  }
+  block_sum2(sq, 0.0, a.part + v * NPART + bx, nullptr);
+}
+
 // ------------------------------------------------------------------ host side
 namespace {
 
@@ -2538,6 +2625,119 @@ int mlp_sgd_t(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* s) {
   return timing_end(ctx, ctx->stream);
 }
 
+// SGLD of hmcx_mlp_sgld_run (sgld.py step inside sgmcmc.py's minibatch loop): mlp_sgd_t's schedule with another
+// last kernel.  Per step the unfused launches of mlp_grad_t on the step's minibatch into a gradient workspace
+// (forward, layer-1 backward, W1 / W2 gradients, the bias / W3 gradients in ONE k_pending launch), then
+// k_mlp_sgld: noise, update, draw store, Σθ² partials, the step's loss and the next step's Philox masks — 8
+// launches per ordinary step with n_out ≤ 32 (9 above: layer 3 takes two).  Each set bit of want_eval[s] adds
+// an evaluation at the updated θ: its masks (PHILOX: hmcx_mlp_masks's launch, slot 0x80000000 + f), mlp_loss_t's
+// forward and k_mlp_sgd_eval.  lpart is written by the gradient forward, read by the k_mlp_sgld behind it and
+// only then rewritten by an evaluation forward (read by its k_mlp_sgd_eval) or the next step: stream order
+// keeps them apart.
+template <typename T>
+int mlp_sgld_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* s) {
+  MlpNet<T> net{};
+  Workspace ws(ctx);
+  double* lpart;
+  MaskSrc<T> ms;
+  const int B = s->B, n_mid = s->n_mid;
+  if (int rc = oneoff_net<T>(ctx, ws, net, s->X, s->y, B, s->n_in, n_mid, s->n_out, nullptr, &lpart, &ms)) return rc;
+  const bool philox = s->mask_mode == HMCX_MLP_MASKS_PHILOX, fixed = s->mask_mode == HMCX_MLP_MASKS_FIXED;
+  const int n3 = 3 * B * n_mid;
+  T *g[6], *mscr = nullptr, *escr = nullptr;
+  double* part;
+  do {                                                         // oneoff_net's takes again, then this call's own
+    ws.reset();
+    mlp_workspace<T>(ws, net);
+    lpart = ws.take<double>(net.nlb);
+    for (int v = 0; v < 6; ++v) g[v] = ws.take<T>((size_t)net.nvar(v));
+    part = ws.take<double>(6 * NPART);
+    if (philox) { mscr = ws.take<T>((size_t)n3); escr = ws.take<T>((size_t)n3); }
+  } while (ws.retry());
+  if (ws.failed) return HMCX_ENOMEM;
+  if (int rc = timing_begin(ctx, ctx->stream)) return rc;
+  T* q[6];
+  MlpSgld<T> k{};
+  for (int v = 0; v < 6; ++v) {
+    q[v] = (T*)s->par.p[v];
+    k.vt.q[v] = q[v]; k.vt.p[v] = s->variant == 1 ? s->mom.p[v] : nullptr; k.vt.qn[v] = g[v]; k.vt.n[v] = net.nvar(v);
+  }
+  for (int i = 0, off = 0; i < 6; ++i) {                       // the noise layout: variable after variable in `order`
+    k.vt.e0[s->order[i]] = off;
+    off += net.nvar(s->order[i]);
+  }
+  k.variant = s->variant; k.noise_mode = s->noise_mode;
+  k.seed = s->seed; k.chain = s->chain;
+  k.part = part; k.lpart = lpart; k.nlb = net.nlb; k.B = B;
+  k.n3 = n3; k.slot = MASK_SLOT0;
+  const T* const X0 = (const T*)s->X;
+  // the masks of a forward: FIXED at `off` of the caller's buffer, PHILOX in `scr`, NONE nothing
+  auto masks_of = [&](int64_t off, const T* scr) {
+    const T* m = fixed ? (const T*)s->masks + off : philox ? scr : nullptr;
+    ms.vals = m;
+    net.vec_masks = n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
+  };
+  const int ng = (n3 + 63) / 64;                               // mask groups: one thread each
+  const unsigned xrows = (unsigned)(((size_t)(ng + 255) / 256 + 1 + NPART - 1) / NPART);
+  if (philox)
+    if (int rc = mlp_masks_t<T>(ctx, B, n_mid, s->seed, s->chain, s->step_base, MASK_SLOT0, mscr)) return rc;
+  int n_eval = 0, n_draw = 0;
+  for (int si = 0; si < s->n_steps; ++si) {
+    net.X = X0 + (size_t)s->row0[si] * s->n_in;
+    net.y = s->y + s->row0[si];
+    net.xw_valid = false;
+    masks_of(fixed ? s->mask_off[si] : 0, mscr);
+    HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, lpart, L3Want{true, true, true, true}));
+    HMCX_HIP(ctx, mlp_ga1<T>(net, q, ms, true));
+    Upd<T> u{};
+    u.half_alpha = (T)(0.5 * s->alpha);
+    for (int v : {0, 2}) {
+      u.W = q[v]; u.G = g[v];
+      HMCX_HIP(ctx, mlp_wgrad<T>(net, q, ms, v, UPD_GRAD, u));
+    }
+    for (int v : {1, 3, 4, 5}) {
+      u.W = q[v]; u.G = g[v];
+      if (!set_pending(net, v, UPD_GRAD, u)) return pend_full(ctx);
+    }
+    HMCX_HIP(ctx, flush_pending(net));
+    const double eps = s->eps[si];
+    k.two_eps = (T)(2.0 * eps);
+    k.half_eps = s->variant == 0 ? (T)(-0.5 * eps) : (T)(0.5 * eps);
+    k.noise = s->noise_mode == HMCX_NOISE_BUFFER ? s->noise + s->noise_off[si] : nullptr;
+    k.step = s->step_base + (uint32_t)si;
+    const bool keep = s->want_draw && s->want_draw[si];
+    for (int v = 0; v < 6; ++v)
+      k.vt.qc[v] = keep ? (void*)((T*)s->draws.p[v] + (size_t)n_draw * (size_t)net.nvar(v)) : nullptr;
+    n_draw += keep ? 1 : 0;
+    const bool next_masks = philox && si + 1 < s->n_steps;
+    k.out_loss = s->out_loss ? s->out_loss + si : nullptr;
+    k.masks = next_masks ? mscr : nullptr;
+    k.mstep = s->step_base + (uint32_t)(si + 1);
+    const unsigned rows = next_masks ? xrows : k.out_loss ? 1u : 0u;
+    hipLaunchKernelGGL(k_mlp_sgld<T>, dim3(NPART, 6 + rows), dim3(256), 0, ctx->stream, k);
+    HMCX_HIP(ctx, hipGetLastError());
+    const int want = s->want_eval ? s->want_eval[si] : 0;
+    // the state after the update on the same minibatch, fresh masks: forward 1, then 2, of the step in call
+    // order (sgmcmc.py:60-62 / 74-76 the log line, :79 the epoch-end negative_log_posterior)
+    for (int bit = 0, f = 1; bit < 2; ++bit) {
+      if (!((want >> bit) & 1)) continue;
+      if (philox)
+        if (int rc = mlp_masks_t<T>(ctx, B, n_mid, s->seed, s->chain, s->step_base + (uint32_t)si,
+                                    MASK_SLOT0 + (uint32_t)f, escr))
+          return rc;
+      masks_of(fixed ? s->eval_mask_off[2 * (size_t)si + (size_t)(f - 1)] : 0, escr);
+      net.xw_valid = false;                                    // W1 moved
+      HMCX_HIP(ctx, mlp_forward<T>(net, q, ms, lpart, L3Want{false, false, false, false}));
+      hipLaunchKernelGGL(k_mlp_sgd_eval, dim3(1), dim3(64), 0, ctx->stream, lpart, net.nlb, B, part,
+                         s->out_eval_loss + n_eval, s->out_eval_sumsq ? s->out_eval_sumsq + 6 * (size_t)n_eval : nullptr);
+      HMCX_HIP(ctx, hipGetLastError());
+      ++n_eval;
+      ++f;
+    }
+  }
+  return timing_end(ctx, ctx->stream);
+}
+
 template <typename T>
 int mlp_loss_t(hmcx_ctx* ctx, const void* X, const int32_t* y, int B, int n_in, int n_mid, int n_out,
                const hmcx_mlp_params* par, const void* masks, double* loss, void* logits) {
@@ -3106,7 +3306,8 @@ int mlp_sghmc_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* s) {
                              const void*, double*, void*);                                                            \
   template int mlp_sghmc_t<T>(hmcx_ctx*, const hmcx_mlp_sghmc_args*);                                                 \
   template int mlp_leapfrog_t<T>(hmcx_ctx*, const hmcx_mlp_leapfrog_args*);                                           \
-  template int mlp_sgd_t<T>(hmcx_ctx*, const hmcx_mlp_sgd_args*);
+  template int mlp_sgd_t<T>(hmcx_ctx*, const hmcx_mlp_sgd_args*);                                                     \
+  template int mlp_sgld_t<T>(hmcx_ctx*, const hmcx_mlp_sgld_args*);
 #if HMCX_MLP_DTYPES & 1
 HMCX_MLP_INSTANTIATE(float)
 #endif

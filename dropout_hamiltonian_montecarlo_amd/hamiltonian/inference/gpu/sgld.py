@@ -10,7 +10,16 @@ of ``sample``, gpu/sgmcmc.py:48), q += p.  The momentum lives on the device next
 
 One SGLD step = one k_fwd + one k_grad launch (hmcx_sgld_run); the log-likelihood the
 reference prints every 10 minibatches costs one extra forward launch on those steps only.
+
+The dropout MLP (``_run_mlp``): one epoch is one hmcx_mlp_sgld_run call — per step hmcx_mlp_grad's unfused
+launches into a gradient workspace and one element-wise kernel that draws the noise and applies the update
+(8 launches), plus one forward per log line and one for the epoch-end negative_log_posterior.  Dropout masks are
+Philox keyed by (seed, chain, global step, forward), ``sample(..., masks='off')`` runs without dropout, and
+``mask_provider`` injects them (parity).  ``keep_every=k`` keeps every k-th sampling step's state on the device
+(``device_draws``, the stacked layout ``mlp.posterior_predictive`` reads).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -22,17 +31,27 @@ from .sgmcmc import RunResult, sgmcmc
 
 class sgld(sgmcmc):
 
+    mask_provider = None    # MLP parity hook: f(global_step, n_forwards) -> [n_fwd, 3, B, n_mid] masks
+
     def __init__(self, model, start_p, path_length=1.0, step_size=0.1, verbose=True,
-                 noise='numpy', seed=0, chain=0, chains=1, variant='cpu'):
+                 noise='numpy', seed=0, chain=0, chains=1, variant='cpu', keep_every=None):
         if variant not in ('cpu', 'gpu'):
             raise ValueError("variant must be 'cpu' (cpu/sgld.py) or 'gpu' (gpu/sgld.py)")
+        if keep_every is not None and int(keep_every) < 1:
+            raise ValueError("keep_every must be None or >= 1")
         self.variant = variant
+        self.keep_every = None if keep_every is None else int(keep_every)   # MLP: device_draws
+        self.device_draws = None
         self._mom = None
+        self._mlp_masks_off = False
+        self._mlp_sampling = None          # inside sample(): [burn-in calls left, sampling steps done, draw chunks]
         super().__init__(model, start_p, path_length=path_length, step_size=step_size, verbose=verbose,
                          noise=noise, seed=seed, chain=chain, chains=chains)
 
     def sample(self, epochs=1, burnin=1, batch_size=1, rng=None, **args):
         self._mom = None                       # p = zeros (gpu/sgmcmc.py:48)
+        if self.model._hmcx_model == 'mlp':
+            return self._sample_mlp(epochs, burnin, batch_size, rng, args)
         return super().sample(epochs=epochs, burnin=burnin, batch_size=batch_size, rng=rng, **args)
 
     def _momentum(self, state):
@@ -41,10 +60,24 @@ class sgld(sgmcmc):
         return self._mom
 
     def _check_vars(self):
+        if self.model._hmcx_model == 'mlp':
+            from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
+            if sorted(self.start.keys()) != sorted(MLP_PARAM_NAMES):
+                raise HmcxError("sgld(mlp): start_p must hold exactly %s" % (MLP_PARAM_NAMES,))
+            if self.chains != 1:
+                raise HmcxError("sgld(mlp): one chain per sampler (chains=1)")
+            for k in self.start:
+                if tuple(self.start[k].shape) != self.model.shapes[k]:
+                    raise HmcxError("sgld(mlp): %s has shape %s, expected %s"
+                                    % (k, tuple(self.start[k].shape), self.model.shapes[k]))
+            self._order = [MLP_PARAM_NAMES.index(k) for k in self.start.keys()]
+            return
         if self.model._hmcx_model != 'softmax' or list(self.start.keys()) != ['weights', 'bias']:
             raise HmcxError("sgld: libhmcx implements the softmax model with start_p keys ['weights', 'bias']")
 
     def _run(self, state, data, rows, eps, rng, batch_size):
+        if self.model._hmcx_model == 'mlp':
+            return self._run_mlp(state, data, rows, eps, rng, batch_size)
         Xd, Yd = data
         W, b = state['weights'], state['bias']
         C = self.chains
@@ -123,6 +156,8 @@ class sgld(sgmcmc):
         zeros) and (q, p) is returned."""
         if self.chains != 1:
             raise HmcxError("step() is the reference's single-chain API; use sample() for chains > 1")
+        if self.model._hmcx_model == 'mlp':
+            return self._step_mlp(state, momentum, rng, args)
         X, y = args['X_train'], args['y_train']
         data = self._upload_data(X, y)
         dev, dt = self.model.device, self.model.dtype
@@ -136,4 +171,157 @@ class sgld(sgmcmc):
             self._mom = {var: (dev_copy(momentum[var]).reshape(st[var].shape) if momentum is not None
                                else torch.zeros_like(st[var])) for var in self.start}
         self._run(st, data, [0], [self.step_size], rng, data[0].shape[0])
+        return st, (self._mom if self.variant == 'gpu' else None)
+
+    # ------------------------------------------------------------------ the dropout MLP
+    @staticmethod
+    def _masks_arg(args):
+        masks = args.get('masks', None)
+        if masks is not None and masks != 'off':
+            raise ValueError("masks must be None or 'off' (inject masks through mask_provider)")
+        return masks == 'off'
+
+    def _sample_mlp(self, epochs, burnin, batch_size, rng, args):
+        """sgmcmc.sample on the MLP: its loop of one call per epoch, with the draws of ``keep_every`` collected
+        from the sampling epochs' calls and the device state / momentum left behind."""
+        self._mlp_masks_off = self._masks_arg(args)
+        self._mlp_sampling = [int(burnin), 0, []]
+        self.device_draws = None
+        try:
+            out = super().sample(epochs=epochs, burnin=burnin, batch_size=batch_size, rng=rng, **args)
+            chunks = self._mlp_sampling[2]
+        finally:
+            self._mlp_sampling = None
+            self._mlp_masks_off = False
+        if self.keep_every is not None:
+            dev, dt = self.model.device, self.model.dtype
+            self.device_draws = {k: (torch.cat([c[k] for c in chunks]) if chunks else
+                                     torch.empty((0,) + self.model.shapes[k], dtype=dt, device=dev))
+                                 for k in self.start}
+        self.last_momentum = self._mom if self.variant == 'gpu' else None
+        return out
+
+    def _run_mlp(self, state, data, rows, eps, rng, batch_size, evals=True):
+        """len(rows) SGLD steps as one hmcx_mlp_sgld_run.  RunResult.ll[j] is the log line's loss (the mean CE
+        at the updated state under fresh masks) where j % log_every == 0, RunResult.nlp[-1] the epoch-end
+        negative_log_posterior; ``evals=False`` (step()) runs neither."""
+        from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
+        m = self.model
+        Xd, yd = data
+        dev = m.device
+        B = int(batch_size)
+        P = sum(int(np.prod(self.start[k].shape)) for k in self.start)
+        n_steps = len(rows)
+        row0 = np.asarray(rows, dtype=np.int64)
+        eps_a = np.asarray(eps, dtype=np.float64)
+        noise_off = np.arange(n_steps, dtype=np.int64) * P
+        noise_d = None
+        if self.noise == 'numpy':
+            # sgld.py:45: rng.normal(0, 2ε, shape) per variable in start order = 2ε·N(0,1) (scaled on the device)
+            noise_d = torch.from_numpy(np.asarray(rng.standard_normal(P * n_steps), dtype=np.float64)).to(dev)
+        want = np.zeros(n_steps, dtype=np.uint8)
+        if evals:
+            want[::self.log_every] |= 1
+            want[-1] |= 2
+        n_fwd = 1 + (want & 1) + (want >> 1)
+        n_evals = int(n_fwd.sum()) - n_steps
+        masks_d = None
+        mask_off, eval_off = np.zeros(n_steps, dtype=np.int64), np.zeros((n_steps, 2), dtype=np.int64)
+        if self._mlp_masks_off:
+            mode = nat.MLP_MASKS_NONE
+        elif self.mask_provider is not None:
+            mode, n3, chunks, off = nat.MLP_MASKS_FIXED, 3 * B * m.n_mid, [], 0
+            for s in range(n_steps):
+                nf = int(n_fwd[s])
+                mk = np.asarray(self.mask_provider(self.global_step + s, nf))
+                if mk.shape != (nf, 3, B, m.n_mid):
+                    raise HmcxError("sgld(mlp): mask_provider must return [%d, 3, %d, %d]" % (nf, B, m.n_mid))
+                chunks.append(mk.reshape(-1))
+                mask_off[s], eval_off[s, 0], eval_off[s, 1] = off, off + n3, off + 2 * n3
+                off += nf * n3
+            masks_d = torch.from_numpy(np.concatenate(chunks)).to(dev, m.dtype)
+        else:
+            mode = nat.MLP_MASKS_PHILOX
+        # keep_every: every k-th sampling step (burn-in calls keep nothing)
+        draw, want_draw = None, None
+        smp = self._mlp_sampling
+        if smp is not None:
+            if smp[0] > 0:
+                smp[0] -= 1
+            else:
+                if self.keep_every is not None:
+                    idx = smp[1] + np.arange(n_steps)
+                    want_draw = ((idx + 1) % self.keep_every == 0).astype(np.uint8)
+                    nd = int(want_draw.sum())
+                    draw = {k: torch.empty((nd,) + m.shapes[k], dtype=m.dtype, device=dev) for k in self.start}
+                    if nd == 0:
+                        want_draw = None
+                smp[1] += n_steps
+        f64 = dict(dtype=torch.float64, device=dev)
+        out_loss = torch.empty(n_steps, **f64)
+        ev_loss, ev_ss = torch.empty(max(n_evals, 1), **f64), torch.empty((max(n_evals, 1), 6), **f64)
+        a = nat.MlpSgldArgs()
+        a.dtype = m.code
+        a.B, a.n_in, a.n_mid, a.n_out, a.n_steps = B, m.n_in, m.n_mid, m.n_out, n_steps
+        for i, v in enumerate(self._order):
+            a.order[i] = v
+        a.variant = 1 if self.variant == 'gpu' else 0
+        a.alpha = m.alpha
+        a.X, a.y = ptr(Xd), ptr(yd)
+        a.row0 = row0.ctypes.data_as(nat.c_i64p)
+        a.eps = eps_a.ctypes.data_as(nat.c_dblp)
+        a.want_eval = want.ctypes.data_as(nat.c_u8p)
+        a.noise_mode = nat.NOISE_BUFFER if self.noise == 'numpy' else nat.NOISE_PHILOX
+        a.noise = ptr(noise_d)
+        a.noise_off = noise_off.ctypes.data_as(nat.c_i64p)
+        a.mask_mode, a.masks = mode, ptr(masks_d)
+        a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
+        a.eval_mask_off = eval_off.ctypes.data_as(nat.c_i64p)
+        a.seed, a.chain, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
+        mom = self._momentum(state) if self.variant == 'gpu' else None
+        for i, k in enumerate(MLP_PARAM_NAMES):
+            a.par.p[i] = state[k].data_ptr()
+            if mom is not None:
+                a.mom.p[i] = mom[k].data_ptr()
+            if want_draw is not None:
+                a.draws.p[i] = draw[k].data_ptr()
+        if want_draw is not None:
+            a.want_draw = want_draw.ctypes.data_as(nat.c_u8p)
+        a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
+        ctx = nat.context(dev)
+        ctx.check(ctx.lib.hmcx_mlp_sgld_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_run")
+        self.global_step += n_steps
+        self.loss_trace = out_loss.cpu().numpy()                          # waits for the call
+        el, ss = ev_loss.cpu().numpy(), ev_ss.cpu().numpy()
+        del noise_d, masks_d
+        if want_draw is not None:
+            smp[2].append(draw)
+        ll, nlp = np.full(n_steps, np.nan), np.full(n_steps, np.nan)
+        e = 0
+        for s in range(n_steps):
+            if want[s] & 1:
+                ll[s] = el[e]
+                e += 1
+            if want[s] & 2:
+                parts = [el[e]] + [ss[e, MLP_PARAM_NAMES.index(k)] for k in self.start]
+                nlp[s] = m.nlp_from_parts(parts, self.start)
+                e += 1
+        if self.trace is not None:
+            self.trace.extend({'L': 1.0, 'A': 1.0, 'accepted': True, 'eps': float(e_)} for e_ in eps)
+        return RunResult(np.ones(n_steps), np.ones(n_steps, dtype=bool), ll, nlp=nlp if evals else None)
+
+    def _step_mlp(self, state, momentum, rng, args):
+        """sgld.step on the MLP: one hmcx_mlp_sgld_run of one step on the given minibatch, no evaluation."""
+        m = self.model
+        data = m._xy(args)
+        st = {k: m._dev(state[k]).reshape(m.shapes[k]).contiguous().clone() for k in self.start}
+        if self.variant == 'gpu':
+            self._mom = {k: (m._dev(momentum[k]).reshape(m.shapes[k]).contiguous().clone() if momentum is not None
+                             else torch.zeros_like(st[k])) for k in self.start}
+        off = self._mlp_masks_off
+        self._mlp_masks_off = self._masks_arg(args)
+        try:
+            self._run_mlp(st, data, [0], [self.step_size], rng, data[0].shape[0], evals=False)
+        finally:
+            self._mlp_masks_off = off
         return st, (self._mom if self.variant == 'gpu' else None)

@@ -652,6 +652,74 @@ typedef struct hmcx_mlp_sgd_args {
 } hmcx_mlp_sgd_args;
 int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a);
 
+/* SGLD on the MLP, an epoch of steps in one call: replaces the loop of hamiltonian/inference/{cpu,gpu}/sgmcmc.py
+ * over sgld.step (cpu/sgld.py:31-46, gpu/sgld.py:11-26).  Per step s on the minibatch rows row0[s] .. row0[s] + B,
+ * with ε = eps[s]:
+ *   g = grad(θ) — the values hmcx_mlp_grad returns for the step's masks (∇ mean CE + ½·alpha·θ), z = P standard
+ *   normals (P = all six variables' elements), then for every element, in dtype T, every product and sum rounded
+ *   once as the NumPy expression rounds them:
+ *     variant 0 (cpu/sgld.py:34-38, rng.normal(0, 2ε)):  p = (T)(2ε)·z;  p = p + (T)(−0.5·ε)·g;  θ = θ + p
+ *     variant 1 (gpu/sgld.py:14-19):  p = ((T)(2ε)·z)·p_prev − (T)(0.5·ε)·g;  θ = θ + p;  p is stored in mom.
+ * Noise: z is laid out variable after variable in `order` (the caller's start_p order, in which draw_momentum
+ * draws), element e = the variable's offset in that layout + its index.
+ *   HMCX_NOISE_BUFFER  step s reads z[e] = noise[noise_off[s] + e] (double, converted to T);
+ *   HMCX_NOISE_PHILOX  z[e] = the Philox normal of (seed, chain, step_base + s, slot 0, e) in T — SGHMC's momentum
+ *                      convention; hmcx_philox_normals (float) / hmcx_philox_normals_f64 (double) return the same
+ *                      stream on the host.
+ * out_loss[s] is the mean CE of the gradient forward (θ before the update).
+ * Evaluations: want_eval[s] is a bit mask, each set bit one more forward on the step's minibatch at the updated θ
+ * under fresh masks.  Bit 0: the outer loop's log line, log_likelihood(q) (sgmcmc.py:60-62,74-76); bit 1: the
+ * epoch-end negative_log_posterior (sgmcmc.py:79).  The forwards of a step are numbered in call order: 0 the
+ * gradient forward, then the bit-0 forward if set, then the bit-1 forward if set.  The e-th evaluation of the call
+ * (step order, bit 0 before bit 1; n_evals set bits in all) writes out_eval_loss[e] = the mean CE (hmcx_mlp_loss's
+ * value) and, where out_eval_sumsq is given, out_eval_sumsq[e][v] = Σθ² (float64, fixed summation order) of
+ * canonical variable v (0=W1 .. 5=b3) — the pieces of negative_log_posterior (mlp.py:80-82), which the caller
+ * composes in its own variable order.
+ * Masks (the HMCX_MLP_MASKS_* values):
+ *   NONE    no dropout;
+ *   FIXED   forward 0 of step s reads masks + mask_off[s], forward f ≥ 1 masks + eval_mask_off[2·s + f − 1]
+ *           (3·B·n_mid values each, dtype);
+ *   PHILOX  forward f of step s uses what hmcx_mlp_masks(ctx, dtype, B, n_mid, seed, chain, step_base + s,
+ *           0x80000000 + f, ·) writes.
+ * Draws: where want_draw[s] is set, the updated θ of step s is also stored, the d-th flagged step of the call at
+ * draws.p[v] + d·n_v (n_v the elements of canonical variable v): the [S][shape] stacked layout hmcx_mlp_predictive
+ * reads.
+ * One call of n steps equals any split into calls that carry par / mom and advance step_base (and the draw
+ * pointers), bit for bit.  Every launch is the unfused one of hmcx_mlp_grad / hmcx_mlp_loss (no cross-workgroup
+ * exchange, nothing that could time out: no out_abort), plus one element-wise launch per step (k_mlp_sgld: the
+ * noise, the update, the draw store, the Σθ² partials, the step's loss and the next step's Philox masks).
+ * n_steps == 0 does nothing.  Stream-ordered; returns once enqueued. */
+typedef struct hmcx_mlp_sgld_args {
+  int dtype;
+  int B, n_in, n_mid, n_out, n_steps;
+  int order[6];               /* canonical variable indices 0=W1 .. 5=b3 in the caller's start order */
+  int variant;                /* 0: cpu/sgld.py, 1: gpu/sgld.py (carried momentum) */
+  double alpha;
+  const void* X;              /* device [N][n_in] */
+  const int32_t* y;           /* device [N] labels */
+  const int64_t* row0;        /* host [n_steps]: minibatch of step s = rows row0[s] .. +B */
+  const double* eps;          /* host [n_steps]: step size of step s */
+  const uint8_t* want_eval;   /* host [n_steps] or NULL: bit 0 = log-line forward, bit 1 = epoch-end forward */
+  int noise_mode;             /* HMCX_NOISE_BUFFER or HMCX_NOISE_PHILOX */
+  const double* noise;        /* device, BUFFER */
+  const int64_t* noise_off;   /* host [n_steps], BUFFER: step s reads noise + noise_off[s] .. + P */
+  int mask_mode;              /* HMCX_MLP_MASKS_NONE / _FIXED / _PHILOX */
+  const void* masks;          /* device (dtype), FIXED */
+  const int64_t* mask_off;    /* host [n_steps], FIXED: masks of step s's gradient forward */
+  const int64_t* eval_mask_off;/* host [n_steps][2], FIXED: masks of forwards 1 and 2 of step s (read where set) */
+  uint64_t seed;
+  uint32_t chain, step_base;
+  hmcx_mlp_params par;        /* state, updated in place */
+  hmcx_mlp_params mom;        /* variant 1: momentum, updated in place (zeros at the start, gpu/sgmcmc.py:48);
+                                 variant 0: all NULL */
+  double* out_loss;           /* device [n_steps] or NULL */
+  double* out_eval_loss;      /* device [n_evals] */
+  double* out_eval_sumsq;     /* device [n_evals][6] or NULL */
+  const uint8_t* want_draw;   /* host [n_steps] or NULL: 1 = store θ after step s */
+  hmcx_mlp_params draws;      /* device, [n_draws][shape] per variable (read where want_draw is given) */
+} hmcx_mlp_sgld_args;
+int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a);
+
 /* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
  * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
  * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
