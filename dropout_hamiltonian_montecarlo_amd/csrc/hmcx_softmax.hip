@@ -248,7 +248,14 @@ __global__ __launch_bounds__(NW * 64) void k_fwd(FwdArgs<T> a) {
       zA[i][j] = y - yb;                                                  // bias sub-step colsum term
       eB[i][j] = y * (zB[i][j] - lse);                                    // softmax.py:19-20
     } else if (mode == FWD_LL) {
-      if (sig) {
+      if (sig && sizeof(T) == 4) {
+        // float32: ŷ rounds to exactly 1 from z = 16.64 on (the clip bound 36.04 is float64's) and
+        // exp(−z) overflows below −88.7, so log(ŷ) or log(1 − ŷ) would see a rounded 0.  The same
+        // terms from the clipped logit: log ŷ = ls(z), log(1 − ŷ) = ls(−z), ls(t) = min(t, 0) − log1p(exp(−|t|))
+        const T z = zA[i][j];
+        const T sp = log1p(exp(-fabs(z)));
+        eA[i][j] = y * (np_min(z, T(0)) - sp) + (T(1) - y) * (np_min(-z, T(0)) - sp);
+      } else if (sig) {
         eA[i][j] = y * log(yh) + (T(1) - y) * log(T(1) - yh);             // logistic.py:71
       } else {
         const T lse = log(sA[i][cc]) + mA[i][cc];

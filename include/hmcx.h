@@ -124,7 +124,9 @@ int hmcx_softmax_predict(hmcx_ctx* ctx, int dtype, const void* X, int B, int D, 
  * net = sigmoid(clip(XW + b)) = 1/(1 + exp(−z)) (:43-55);  grad = −(Xᵀ(y − net) − alpha·θ) (:24-41). */
 int hmcx_logistic_grad(hmcx_ctx* ctx, int dtype, const void* X, const void* y, int B, int D, int C,
                        const void* W, const void* b, double alpha, void* gW, void* gb);
-/* ll[c] = Σ_rows y·log(net) + (1 − y)·log(1 − net)  (:64-72), device double[C]. */
+/* ll[c] = Σ_rows y·log(net) + (1 − y)·log(1 − net)  (:64-72), device double[C].  HMCX_F32 takes both
+ * logarithms from the clipped logit z (log net = min(z, 0) − log1p(exp(−|z|)), log(1 − net) likewise at −z):
+ * a float32 net is exactly 1 from z = 16.64 on, far inside the clip bound. */
 int hmcx_logistic_loglik(hmcx_ctx* ctx, int dtype, const void* X, const void* y, int B, int D, int C,
                          const void* W, const void* b, double* ll);
 /* prob [B][C] = net (predict(prob=True) of :75-87, before batching). */

@@ -1,7 +1,17 @@
 """GPU parity of the fused samplers against the NumPy oracle and the reference's golden runs.
 
 Integer bookkeeping (path lengths, accept flags) must be bit-exact; float64 states within
-rel 1e-9 (GEMM summation order only); float32 runs are compared statistically/loosely."""
+rel 1e-9 (GEMM summation order only); float32 runs are compared statistically/loosely, except
+test_sgld_f32_paths_vs_oracle: float32 SGLD at ragged shapes on the kernel-per-phase path and both forms of
+the wide path, within max(16·d, 1e-5·s) of the float64 oracle (d: the oracle run in float32 against itself
+in float64; tests/_linear_cases.py).  Measured on MI355X, largest err/d over the seven shapes:
+  states   1.0 on all three paths, at (K, D, B) = (2, 1, 1): err = d = 3.7e-9; err/tolerance at most 0.046
+           (kernel-per-phase, (38, 2000, 130): err 1.4e-6, d 1.9e-6), 0.021 on the wide paths
+  logp     1.8 kernel-per-phase, 2.3 wide, both at (64, 300, 40): err 1.1e-7 / 1.4e-7, d 5.9e-8;
+           err/tolerance at most 0.002
+  ll       the same ratios (ll is logp without the prior's constant); err/tolerance at most 0.047
+The fused and the three-launch wide path agree to every printed digit.  16·d is the bound on the states at
+D = 785 and D = 2000; no output came near it."""
 import io
 import os
 
@@ -15,6 +25,8 @@ torch = pytest.importorskip("torch")
 from oracle import inputs as gi  # noqa: E402
 from oracle import models as om  # noqa: E402
 from oracle import samplers as osm  # noqa: E402
+
+import _linear_cases as lc  # noqa: E402
 
 
 def _gpu_classes():
@@ -291,6 +303,34 @@ def test_sgld_wide_equals_kernel_path_philox(dtype, monkeypatch):
     for v in ("weights", "bias"):
         np.testing.assert_allclose(pw[v], ps[v], **tol)
     np.testing.assert_allclose(lw, ls, rtol=1e-9 if dtype == "f64" else 1e-4)
+
+
+@pytest.mark.parametrize("wide,fuse", lc.SGLD_PATHS, ids=["kernels", "wide-fused", "wide-3-launches"])
+@pytest.mark.parametrize("K,D,B", lc.SGLD_SHAPES)
+def test_sgld_f32_paths_vs_oracle(K, D, B, wide, fuse, monkeypatch):
+    """float32 SGLD on the kernel-per-phase path and on both forms of the wide path at ragged shapes (one
+    row and one feature; K < 16, K one past a class tile, K = 64; D not a multiple of 4, of 16, of the
+    128-feature slice; partial row blocks) against oracle.samplers.sgld in float64 on the float32-rounded
+    data.  step_size 1e-2: from the zero start a smaller step leaves the state almost pure noise and a wrong
+    gradient within the tolerance.  States, logp and the log-likelihood inside logp within max(16·d, 1e-5·s)
+    (tests/_linear_cases.py::sgld_tolerances; d from the oracle run in float32 throughout)."""
+    monkeypatch.setenv("HMCX_SGLD_WIDE", wide)
+    if fuse is None:
+        monkeypatch.delenv("HMCX_WIDE_FUSE", raising=False)
+    else:
+        monkeypatch.setenv("HMCX_WIDE_FUSE", fuse)
+    c = lc.sgld_config(K, D, B)
+    s_r, logp_r = lc.sgld_reference(K, D, B)
+    tol, d = lc.sgld_tolerances(K, D, B)
+    post_g, logp_g, _, _ = _run_gpu(c, dtype=torch.float32)
+    s_g = np.concatenate([post_g["weights"].reshape(c["epochs"], -1), post_g["bias"]], axis=1)
+    err = {"states": float(np.max(np.abs(s_g - s_r))), "logp": float(np.max(np.abs(logp_g - logp_r))),
+           "ll": float(np.max(np.abs(lc.sgld_loglik(K, D, B, logp_g) - lc.sgld_loglik(K, D, B, logp_r))))}
+    for o in ("states", "logp", "ll"):
+        print("sgld f32 K %d D %d B %d wide %s fuse %s %s: err %.3e, d %.3e, err/d %.3g, allowed %.3e" % (
+            K, D, B, wide, fuse, o, err[o], d[o], err[o] / d[o] if d[o] > 0 else float("inf"), tol[o]))
+    for o in ("states", "logp", "ll"):
+        assert err[o] <= tol[o], (o, err[o], tol[o])
 
 
 def _run_variant_oracle(c):
