@@ -713,20 +713,30 @@ __device__ __forceinline__ void mm_body(const MMArgs<T>& a, const PR& pr, const 
     const int base_rb = rb * S * items;
     if (a.force_abort && pbid == 0 && tid == 0)                  // test knob: this launch never completes
       __hip_atomic_store(a.abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < items && !(a.force_abort && pbid == 0)) {
-      const int r = tid / No, o = tid - r * No;
-      T zp = T(0);
+    // items reaches 1024 at n_out = 32, twice the workgroup: two passes, and every put of a thread goes out
+    // before its first poll (the other slices of the row block wait for them)
+#pragma unroll
+    for (int u = 0; u < 1024 / MM_NT; ++u) {
+      const int e = tid + MM_NT * u;
+      if (e < items && !(a.force_abort && pbid == 0)) {
+        const int r = e / No, o = e - r * No;
+        T zp = T(0);
 #pragma unroll 8
-      for (int c = 0; c < 32; ++c) zp += d3t[r * 33 + c] * w3s[o * 32 + c];
-      gx_put(rs, base_rb + s * items + tid, (double)zp, a.ep);
+        for (int c = 0; c < 32; ++c) zp += d3t[r * 33 + c] * w3s[o * 32 + c];
+        gx_put(rs, base_rb + s * items + e, (double)zp, a.ep);
+      }
     }
     stamp(2);
     stamp(3);
-    if (tid < items) {
-      const int r = tid / No, o = tid - r * No;
-      double sum = 0.0;
-      (void)gx_poll_sum(rs, base_rb + tid, items, S, a.ep, a.abort_flag, &sum);   // a timeout raises the
-      zt[r * 33 + o] = (m0 + r < a.M) ? (T)sum + b3s[o] : T(0);                   // MLP abort word
+#pragma unroll 1
+    for (int u = 0; u < 1024 / MM_NT; ++u) {
+      const int e = tid + MM_NT * u;
+      if (e < items) {
+        const int r = e / No, o = e - r * No;
+        double sum = 0.0;
+        (void)gx_poll_sum(rs, base_rb + e, items, S, a.ep, a.abort_flag, &sum);   // a timeout raises the
+        zt[r * 33 + o] = (m0 + r < a.M) ? (T)sum + b3s[o] : T(0);                 // MLP abort word
+      }
     }
     __syncthreads();
     stamp(4);

@@ -121,6 +121,12 @@ BY_NAME = {f.name: f for f in FIXTURES}
 NEAR_MISS = [(16, 32, 17, 20), (12, 32, 5, 20), (16, 32, 5, 18), (16, 48, 5, 20)]
 NEAR_MISS_ALPHA, NEAR_MISS_SEED = 0.01, 51
 
+# The fused layer-2/3 launch (k_mm, MM_L23) past 16 classes, where its 32 × n_out logit items outnumber the
+# workgroup's 512 threads (n_in, n_mid, n_out, B): one, two and three column slices; full and partial row
+# blocks; 30, 21 and 16 rows of a block inside the first 512 items.  Recipe as for NEAR_MISS.
+WIDE_CLASS = [(16, 32, 17, 32), (16, 64, 24, 36), (24, 96, 32, 70), (16, 32, 32, 33)]
+WIDE_CLASS_ALPHA, WIDE_CLASS_SEED = 0.01, 51
+
 PERMUTED = ['/l3/b', '/l1/W', '/l2/b', '/l3/W', '/l1/b', '/l2/W']
 
 
@@ -162,6 +168,12 @@ def _fixture_oracle(name, order):
 def fixture_oracle(fx, order=None):
     """The oracle run of a fixture (computed once per process and shared: treat it as read-only)."""
     return _fixture_oracle(fx.name, tuple(order) if order is not None else None)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_class_oracle(shape):
+    """The oracle run of a WIDE_CLASS shape: one call of three steps (computed once, read-only)."""
+    return oracle_run(*shape, WIDE_CLASS_ALPHA, WIDE_CLASS_SEED, n_batches=3, epochs=1)
 
 
 def margins(trace):

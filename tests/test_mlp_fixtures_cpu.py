@@ -67,6 +67,22 @@ def test_permuted_order_fixtures_also_mix():
         assert min(fx.margins(tr)) >= MARGIN, f.name
 
 
+def test_wide_class_shapes_take_three_accepted_trajectories():
+    """The fused-launch shapes with 17 to 32 classes (test_gpu_mlp_accept.py): path lengths [3, 2, 2], every
+    step accepted, no decision within 11 of flipping; every shape has more logit items per row block than the
+    fused workgroup has threads, and rows of a block that lie past the first 512 items."""
+    for shape in fx.WIDE_CLASS:
+        n_in, n_mid, n_out, B = shape
+        tr = fx.wide_class_oracle(shape).trace
+        assert [t["L"] for t in tr] == [3, 2, 2], shape
+        assert all(t["accepted"] for t in tr), shape
+        assert min(fx.margins(tr)) > 11, shape
+        assert 16 < n_out <= 32 and 32 * n_out > 512 and min(B, 32) > 512 // n_out, shape
+    assert {-(-s[1] // 32) for s in fx.WIDE_CLASS} == {1, 2, 3}                 # column slices
+    assert {512 // s[2] for s in fx.WIDE_CLASS} == {30, 21, 16}                 # rows inside the first 512 items
+    assert any(s[3] % 32 == 0 for s in fx.WIDE_CLASS) and any(s[3] % 32 for s in fx.WIDE_CLASS)
+
+
 def test_near_miss_shapes_have_real_robust_steps():
     """The four shapes just outside fwdr_ok (test_gpu_mlp_accept.py) run three real trajectories whose
     flags do not hang on rounding either."""
