@@ -1212,6 +1212,61 @@ int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a) {
   return a->dtype == HMCX_F64 ? mlp_sgld_t<double>(ctx, a) : mlp_sgld_t<float>(ctx, a);
 }
 
+int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
+  if (rc) return rc;
+  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: n_steps < 0");
+  if (a->C < 1 || a->C > 64) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: C must be 1 .. 64");
+  if ((uint64_t)a->chain0 + (uint64_t)a->C > 0x100000000ULL)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: chain0 + C wraps 2^32");
+  if ((uint64_t)a->step_base + (uint64_t)a->n_steps > 0x100000000ULL)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: step_base + n_steps wraps 2^32");
+  if ((long long)a->n_mid * a->n_in + (long long)a->n_mid * a->n_mid + (long long)a->n_out * a->n_mid +
+          2LL * a->n_mid + a->n_out > 0x7fffffffLL)
+    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp sgld chains: more than 2^31 - 1 parameters");
+  if (a->variant != 0 && a->variant != 1)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: variant must be 0 or 1");
+  if (!a->X || !a->y || !a->row0 || !a->eps || !mlp_par_ok(&a->par) || (a->variant == 1 && !mlp_par_ok(&a->mom)))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: null pointer");
+  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: bad noise_mode");
+  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: BUFFER noise mode needs noise and noise_off");
+  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
+      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: bad mask_mode");
+  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: FIXED masks need masks and mask_off");
+  if (a->want_eval && !a->out_eval_loss)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_eval needs out_eval_loss");
+  if (a->want_eval && a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->eval_mask_off)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: FIXED masks with want_eval need eval_mask_off");
+  if (a->want_draw && !mlp_par_ok(&a->draws))
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_draw needs draws");
+  int seen = 0;
+  for (int i = 0; i < 6; ++i) {
+    const int v = a->order[i];
+    if (v < 0 || v > 5 || ((seen >> v) & 1))
+      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: order must be a permutation of 0..5");
+    seen |= 1 << v;
+  }
+  int64_t n_draws = 0;
+  for (int s = 0; s < a->n_steps; ++s) {
+    if (a->row0[s] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: negative row0");
+    if (a->noise_mode == HMCX_NOISE_BUFFER && a->noise_off[s] < 0)
+      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: negative noise_off");
+    if (a->want_eval && a->want_eval[s] > 3)
+      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_eval holds bits 0 and 1");
+    if (a->want_draw && a->want_draw[s]) ++n_draws;
+  }
+  if (n_draws > a->draw_stride)
+    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: draw_stride below the call's flagged steps");
+  if (a->n_steps == 0) return HMCX_OK;
+  return a->dtype == HMCX_F64 ? mlp_sgld_chains_t<double>(ctx, a) : mlp_sgld_chains_t<float>(ctx, a);
+}
+
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   HMCX_GUARD_CTX(ctx);
   if (!a) return set_error(ctx, HMCX_EINVAL, "null args");

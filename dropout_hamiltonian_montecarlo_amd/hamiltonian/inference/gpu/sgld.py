@@ -17,6 +17,16 @@ launches into a gradient workspace and one element-wise kernel that draws the no
 Philox keyed by (seed, chain, global step, forward), ``sample(..., masks='off')`` runs without dropout, and
 ``mask_provider`` injects them (parity).  ``keep_every=k`` keeps every k-th sampling step's state on the device
 (``device_draws``, the stacked layout ``mlp.posterior_predictive`` reads).
+
+Several MLP chains (``chains=C``, 1 < C ≤ 64): one hmcx_mlp_sgld_chains_run per epoch, the chains as the problems
+of batched launches (groups of at most 6) on shared minibatches.  ``start_p[var]`` is the variable's shape (every
+chain starts there) or ``[C, *shape]``; the device state, ``last_state`` and ``last_momentum`` are ``[C, *shape]``,
+``posterior[var]`` is ``[C, epochs, *shape]``, ``logp`` ``[C, epochs]``, ``loss_trace`` ``[n_steps, C]`` and
+``device_draws[var]`` ``[C, T, *shape]`` (one buffer, written in place).  With Philox noise and masks chain c is,
+bit for bit, the one-chain sampler with ``chain=chain + c``; ``noise='numpy'`` and ``mask_provider`` feed every
+chain the same values (replicas, a parity mode), so ``noise='numpy'`` takes per-chain starts only: one shared
+start under one noise stream raises, as ``chains=2`` on the MLP always did.  ``chain_diagnostics`` gives split-R̂
+and ESS of the kept draws on the device.
 """
 import ctypes
 
@@ -45,6 +55,7 @@ class sgld(sgmcmc):
         self._mom = None
         self._mlp_masks_off = False
         self._mlp_sampling = None          # inside sample(): [burn-in calls left, sampling steps done, draw chunks]
+        self._mlp_draw_buf = None          # inside sample(), chains > 1: the [C, T, *shape] draw buffers
         super().__init__(model, start_p, path_length=path_length, step_size=step_size, verbose=verbose,
                          noise=noise, seed=seed, chain=chain, chains=chains)
 
@@ -64,16 +75,43 @@ class sgld(sgmcmc):
             from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
             if sorted(self.start.keys()) != sorted(MLP_PARAM_NAMES):
                 raise HmcxError("sgld(mlp): start_p must hold exactly %s" % (MLP_PARAM_NAMES,))
-            if self.chains != 1:
-                raise HmcxError("sgld(mlp): one chain per sampler (chains=1)")
+            C = self.chains
+            if C > 64:
+                raise HmcxError("sgld(mlp): at most 64 chains per sampler")
             for k in self.start:
-                if tuple(self.start[k].shape) != self.model.shapes[k]:
-                    raise HmcxError("sgld(mlp): %s has shape %s, expected %s"
-                                    % (k, tuple(self.start[k].shape), self.model.shapes[k]))
+                shape, want = tuple(self.start[k].shape), self.model.shapes[k]
+                if shape != want and not (C > 1 and shape == (C,) + want):
+                    raise HmcxError("sgld(mlp): %s has shape %s, expected %s%s"
+                                    % (k, shape, want, " or %s" % ((C,) + want,) if C > 1 else ""))
             self._order = [MLP_PARAM_NAMES.index(k) for k in self.start.keys()]
+            if C > 1 and self.noise == 'numpy' and all(tuple(v.shape) == self.model.shapes[k]
+                                                       for k, v in self.start.items()):
+                # the host noise stream drives every chain (replicas): from one shared start the chains would be
+                # copies of one another in all but their dropout masks, which says nothing about convergence
+                raise HmcxError("sgld(mlp): chains=%d with noise='numpy' replays one noise stream in every chain; "
+                                "give per-chain starts [%d, *shape] or use noise='philox'" % (C, C))
+            if C > 1:
+                # one start per chain, [C, *shape]; self.start keeps the per-chain shapes (chain 0's values)
+                self._mlp_start = {k: np.array(np.broadcast_to(v, (C,) + self.model.shapes[k]))
+                                   for k, v in self.start.items()}
+                self.start = {k: v[0] for k, v in self._mlp_start.items()}
             return
         if self.model._hmcx_model != 'softmax' or list(self.start.keys()) != ['weights', 'bias']:
             raise HmcxError("sgld: libhmcx implements the softmax model with start_p keys ['weights', 'bias']")
+
+    def _mlp_chains(self):
+        return self.model._hmcx_model == 'mlp' and self.chains > 1
+
+    def _init_state(self):
+        if not self._mlp_chains():
+            return super()._init_state()
+        dt, dev = self.model.dtype, self.model.device
+        return {k: torch.as_tensor(v).to(dev, dt).contiguous().clone() for k, v in self._mlp_start.items()}
+
+    def _state_to_host(self, state):
+        if not self._mlp_chains():
+            return super()._state_to_host(state)
+        return {k: state[k].detach().cpu().numpy().astype(np.float64) for k in self.start}   # [C, *shape]
 
     def _run(self, state, data, rows, eps, rng, batch_size):
         if self.model._hmcx_model == 'mlp':
@@ -187,13 +225,24 @@ class sgld(sgmcmc):
         self._mlp_masks_off = self._masks_arg(args)
         self._mlp_sampling = [int(burnin), 0, []]
         self.device_draws = None
+        buf = None
+        if self.chains > 1 and self.keep_every is not None:
+            # the draws of every chain in one buffer [C, T, *shape] the calls write in place
+            n_rows = len(range(0, args['X_train'].shape[0] - int(batch_size) + 1, int(batch_size)))
+            T = int(epochs) * n_rows // self.keep_every
+            buf = {k: torch.empty((self.chains, T) + self.model.shapes[k], dtype=self.model.dtype,
+                                  device=self.model.device) for k in self.start}
+        self._mlp_draw_buf = buf
         try:
             out = super().sample(epochs=epochs, burnin=burnin, batch_size=batch_size, rng=rng, **args)
             chunks = self._mlp_sampling[2]
         finally:
             self._mlp_sampling = None
             self._mlp_masks_off = False
-        if self.keep_every is not None:
+            self._mlp_draw_buf = None
+        if buf is not None:
+            self.device_draws = buf
+        elif self.keep_every is not None:
             dev, dt = self.model.device, self.model.dtype
             self.device_draws = {k: (torch.cat([c[k] for c in chunks]) if chunks else
                                      torch.empty((0,) + self.model.shapes[k], dtype=dt, device=dev))
@@ -204,7 +253,8 @@ class sgld(sgmcmc):
     def _run_mlp(self, state, data, rows, eps, rng, batch_size, evals=True):
         """len(rows) SGLD steps as one hmcx_mlp_sgld_run.  RunResult.ll[j] is the log line's loss (the mean CE
         at the updated state under fresh masks) where j % log_every == 0, RunResult.nlp[-1] the epoch-end
-        negative_log_posterior; ``evals=False`` (step()) runs neither."""
+        negative_log_posterior; ``evals=False`` (step()) runs neither.  chains > 1: one
+        hmcx_mlp_sgld_chains_run on the stacked state, ll / nlp / loss_trace with a trailing chain axis."""
         from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
         m = self.model
         Xd, yd = data
@@ -243,7 +293,8 @@ class sgld(sgmcmc):
         else:
             mode = nat.MLP_MASKS_PHILOX
         # keep_every: every k-th sampling step (burn-in calls keep nothing)
-        draw, want_draw = None, None
+        C = self.chains
+        draw, want_draw, d0 = None, None, 0
         smp = self._mlp_sampling
         if smp is not None:
             if smp[0] > 0:
@@ -253,14 +304,24 @@ class sgld(sgmcmc):
                     idx = smp[1] + np.arange(n_steps)
                     want_draw = ((idx + 1) % self.keep_every == 0).astype(np.uint8)
                     nd = int(want_draw.sum())
-                    draw = {k: torch.empty((nd,) + m.shapes[k], dtype=m.dtype, device=dev) for k in self.start}
+                    if C == 1:
+                        draw = {k: torch.empty((nd,) + m.shapes[k], dtype=m.dtype, device=dev) for k in self.start}
+                    else:                      # draw d0 onward of every chain's row of the [C, T, *shape] buffer
+                        draw, d0 = self._mlp_draw_buf, smp[1] // self.keep_every
                     if nd == 0:
                         want_draw = None
                 smp[1] += n_steps
         f64 = dict(dtype=torch.float64, device=dev)
-        out_loss = torch.empty(n_steps, **f64)
-        ev_loss, ev_ss = torch.empty(max(n_evals, 1), **f64), torch.empty((max(n_evals, 1), 6), **f64)
-        a = nat.MlpSgldArgs()
+        if C == 1:
+            out_loss = torch.empty(n_steps, **f64)
+            ev_loss, ev_ss = torch.empty(max(n_evals, 1), **f64), torch.empty((max(n_evals, 1), 6), **f64)
+            a = nat.MlpSgldArgs()
+            a.chain = self.chain
+        else:
+            out_loss = torch.empty((n_steps, C), **f64)
+            ev_loss, ev_ss = torch.empty((max(n_evals, 1), C), **f64), torch.empty((max(n_evals, 1), C, 6), **f64)
+            a = nat.MlpSgldChainsArgs()
+            a.C, a.chain0 = C, self.chain
         a.dtype = m.code
         a.B, a.n_in, a.n_mid, a.n_out, a.n_steps = B, m.n_in, m.n_mid, m.n_out, n_steps
         for i, v in enumerate(self._order):
@@ -277,38 +338,66 @@ class sgld(sgmcmc):
         a.mask_mode, a.masks = mode, ptr(masks_d)
         a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
         a.eval_mask_off = eval_off.ctypes.data_as(nat.c_i64p)
-        a.seed, a.chain, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
+        a.seed, a.step_base = self.seed, self.global_step & 0xFFFFFFFF
         mom = self._momentum(state) if self.variant == 'gpu' else None
         for i, k in enumerate(MLP_PARAM_NAMES):
             a.par.p[i] = state[k].data_ptr()
             if mom is not None:
                 a.mom.p[i] = mom[k].data_ptr()
             if want_draw is not None:
-                a.draws.p[i] = draw[k].data_ptr()
+                a.draws.p[i] = draw[k][:, d0:].data_ptr() if C > 1 else draw[k].data_ptr()
         if want_draw is not None:
             a.want_draw = want_draw.ctypes.data_as(nat.c_u8p)
+            if C > 1:
+                a.draw_stride = draw[MLP_PARAM_NAMES[0]].shape[1]
         a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
         ctx = nat.context(dev)
-        ctx.check(ctx.lib.hmcx_mlp_sgld_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_run")
+        if C == 1:
+            ctx.check(ctx.lib.hmcx_mlp_sgld_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_run")
+        else:
+            ctx.check(ctx.lib.hmcx_mlp_sgld_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_chains_run")
         self.global_step += n_steps
-        self.loss_trace = out_loss.cpu().numpy()                          # waits for the call
+        self.loss_trace = out_loss.cpu().numpy()                          # waits for the call; C > 1: [n_steps, C]
         el, ss = ev_loss.cpu().numpy(), ev_ss.cpu().numpy()
         del noise_d, masks_d
-        if want_draw is not None:
+        if want_draw is not None and C == 1:
             smp[2].append(draw)
-        ll, nlp = np.full(n_steps, np.nan), np.full(n_steps, np.nan)
+        shape = (n_steps,) if C == 1 else (n_steps, C)
+        ll, nlp = np.full(shape, np.nan), np.full(shape, np.nan)
         e = 0
         for s in range(n_steps):
             if want[s] & 1:
                 ll[s] = el[e]
                 e += 1
             if want[s] & 2:
-                parts = [el[e]] + [ss[e, MLP_PARAM_NAMES.index(k)] for k in self.start]
-                nlp[s] = m.nlp_from_parts(parts, self.start)
+                for c in range(C):
+                    ec, sc = (el[e], ss[e]) if C == 1 else (el[e, c], ss[e, c])
+                    parts = [ec] + [sc[MLP_PARAM_NAMES.index(k)] for k in self.start]
+                    if C == 1:
+                        nlp[s] = m.nlp_from_parts(parts, self.start)
+                    else:
+                        nlp[s, c] = m.nlp_from_parts(parts, self.start)
                 e += 1
         if self.trace is not None:
             self.trace.extend({'L': 1.0, 'A': 1.0, 'accepted': True, 'eps': float(e_)} for e_ in eps)
         return RunResult(np.ones(n_steps), np.ones(n_steps, dtype=bool), ll, nlp=nlp if evals else None)
+
+    def chain_diagnostics(self, vars=None):
+        """{var: (split_rhat, ess)} of the kept draws (``device_draws``, [C, T, *shape]), each of the variable's
+        shape, computed on the device one variable at a time (diagnostics.device_diagnostics)."""
+        from dropout_hamiltonian_montecarlo_amd import diagnostics
+        d = self.device_draws
+        if d is None:
+            raise HmcxError("chain_diagnostics: no draws (sample with keep_every)")
+        out = {}
+        for k in (list(d.keys()) if vars is None else list(vars)):
+            t = d[k] if self.chains > 1 else d[k][None]
+            if t.shape[1] < 4:
+                raise HmcxError("chain_diagnostics: needs at least 4 draws per chain, has %d" % t.shape[1])
+            shape = tuple(t.shape[2:])
+            _, sr, es = diagnostics.device_diagnostics(t.reshape(t.shape[0], t.shape[1], -1).to(torch.float64))
+            out[k] = (sr.reshape(shape), es.reshape(shape))
+        return out
 
     def _step_mlp(self, state, momentum, rng, args):
         """sgld.step on the MLP: one hmcx_mlp_sgld_run of one step on the given minibatch, no evaluation."""

@@ -722,6 +722,62 @@ typedef struct hmcx_mlp_sgld_args {
 } hmcx_mlp_sgld_args;
 int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a);
 
+/* C chains of hmcx_mlp_sgld_run in one call (extension; the reference runs one chain per process).  The chains
+ * take the same steps on the same minibatches row0[s] with the same eps[s]; every field hmcx_mlp_sgld_args also
+ * has means what it means there.
+ * State: par.p[v] holds C stacked copies [C][shape_v], chain-major and contiguous (the [S][shape] layout
+ * hmcx_mlp_predictive reads), updated in place; mom.p[v] the same for variant 1 (all NULL for variant 0).
+ * Chains: with PHILOX noise and PHILOX masks chain c is bit for bit the one-chain hmcx_mlp_sgld_run with
+ * chain = chain0 + c and the same seed, step_base and want_eval — state, momentum, out_loss, the evaluation
+ * outputs and the draws, in float64 and float32, both variants — so the result of chain c depends neither on C
+ * nor on how the chains are grouped into launches.  BUFFER noise and FIXED masks are shared by all chains
+ * (noise_off[s], mask_off[s] and eval_mask_off[s][2] as in the one-chain call): the chains are replicas apart
+ * from their start.
+ * Outputs: out_loss [n_steps][C], out_eval_loss [n_evals][C], out_eval_sumsq [n_evals][C][6].  Draws: the d-th
+ * flagged step of chain c is stored at draws.p[v] + (c·draw_stride + d)·n_v; draw_stride is the caller's draws
+ * per chain, so one [C][T][shape] buffer serves a whole run with the pointers advanced from call to call.
+ * One call of n steps equals any split into calls that carry par / mom and advance step_base and the draw
+ * pointers, bit for bit.
+ * Schedule: the chains are the problems of batched launches, in groups of at most 6 chains; per step and group
+ * the one-chain schedule with every launch widened over the group's chains (layer 1, layer 2, layer 3 +
+ * cross-entropy, layer-1 backward, the W1 and W2 gradients, the bias / W3 gradients, the update: 8 launches
+ * with n_out ≤ 32; above, layer 3 runs chain by chain).  Only unfused launches: no cross-workgroup exchange, no
+ * spin-wait, no abort word.
+ * 1 ≤ C ≤ 64; chain0 + C and step_base + n_steps must not wrap 2^32; want_draw needs draw_stride ≥ the call's
+ * flagged steps.  Invalid arguments return a negative code, set hmcx_last_error and launch nothing.
+ * n_steps == 0 does nothing.  Stream-ordered; returns once enqueued. */
+typedef struct hmcx_mlp_sgld_chains_args {
+  int dtype;
+  int B, n_in, n_mid, n_out, n_steps;
+  int C;                      /* chains, 1 .. 64 */
+  int order[6];
+  int variant;
+  double alpha;
+  const void* X;
+  const int32_t* y;
+  const int64_t* row0;
+  const double* eps;
+  const uint8_t* want_eval;
+  int noise_mode;
+  const double* noise;        /* device, BUFFER: shared by the chains */
+  const int64_t* noise_off;
+  int mask_mode;
+  const void* masks;          /* device (dtype), FIXED: shared by the chains */
+  const int64_t* mask_off;
+  const int64_t* eval_mask_off;
+  uint64_t seed;
+  uint32_t chain0, step_base; /* chain c draws under Philox chain chain0 + c */
+  hmcx_mlp_params par;        /* [C][shape_v] per variable, updated in place */
+  hmcx_mlp_params mom;        /* variant 1: [C][shape_v]; variant 0: all NULL */
+  double* out_loss;           /* device [n_steps][C] or NULL */
+  double* out_eval_loss;      /* device [n_evals][C] */
+  double* out_eval_sumsq;     /* device [n_evals][C][6] or NULL */
+  const uint8_t* want_draw;
+  hmcx_mlp_params draws;      /* device, [C][draw_stride][shape_v] per variable (read where want_draw is given) */
+  int64_t draw_stride;        /* draws per chain of the caller's buffer */
+} hmcx_mlp_sgld_chains_args;
+int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a);
+
 /* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
  * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
  * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
