@@ -3,7 +3,7 @@
 // entropy of the draws (their difference is the mutual information) and, with labels, the log pointwise
 // predictive density and each draw's cross-entropy and hit count — one call, nothing per draw on the host.
 //
-// The network is hmcx_mlp.hip's (names there: a1 = X·W1ᵀ + b1, h1 = max(a1·m0, 0), h2 = max((h1·W2ᵀ + b2)·m1, 0),
+// The network is hmcx_mlp.hip's (names in hmcx_mlp_kernels.h: a1 = X·W1ᵀ + b1, h1 = max(a1·m0, 0), h2 = max((h1·W2ᵀ + b2)·m1, 0),
 // d3 = h2·m2, z = d3·W3ᵀ + b3).  The softmax of a row and everything summed over draws or rows is float64
 // for both dtypes; every sum has a fixed order (no atomics, no exchange between workgroups: what crosses
 // workgroups is a partial that a later launch sums in index order), so equal calls give equal bits.
@@ -193,7 +193,7 @@ __host__ __device__ inline PfLds pf_lds(int n_in, int n_mid, size_t elt) {
   return l;
 }
 
-// k offset, inside a 16-wide k chunk, of MFMA step u for lane group lg (hmcx_mlp.hip's kmap: each lane's k
+// k offset, inside a 16-wide k chunk, of MFMA step u for lane group lg (hmcx_mlp_kernels.h's kmap: each lane's k
 // values are contiguous, 4 floats or 2 + 2 doubles, so an operand along k is one or two 16-byte loads).
 template <typename T> __device__ inline int pf_kmap(int u, int lg);
 template <> __device__ inline int pf_kmap<float>(int u, int lg) { return 4 * lg + u; }

@@ -2,7 +2,8 @@
 tests/test_gpu_mlp_kernels.py drives hmcx_mlp_grad / hmcx_mlp_loss with them, tests/test_mlp_cases_cpu.py checks
 their preconditions on the CPU.  Needs neither a GPU nor torch.
 
-Launch mirror.  ``launches`` restates the host code of csrc/hmcx_mlp.hip that decides what a one-off call
+Launch mirror.  ``launches`` restates the host code of csrc/hmcx_mlp.hip (kernel side: csrc/hmcx_mlp_kernels.h,
+cited by function name) that decides what a one-off call
 (mlp_grad_t / mlp_loss_t: the unfused launches) runs for a shape, dtype, mask kind and mask alignment: per
 k_mm launch the epilogue, the operand vector paths (AV, BV), the XCD placement, the K range each of the eight
 waves takes, and for layer 3 the narrow (MM_L3CE) / wide (k_l3_wide) kernel with its column slices, the ``wl``
@@ -22,7 +23,7 @@ import numpy as np
 from oracle import models as om
 
 ALPHA = 0.01
-MM_NW, MM_NT = 8, 512                     # hmcx_mlp.hip:46-47
+MM_NW, MM_NT = 8, 512                     # hmcx_mlp_kernels.h
 UNIT = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}
 F32_CAP = 2e-4                            # of the largest entry (tests/test_gpu_mlp.py): never looser than this
 F32_MARGIN = 4                            # × the measured worst err / bound (tests/test_gpu_mlp_accept.py)
@@ -33,7 +34,7 @@ OUTPUTS = GRADS + ("loss", "logits")
 
 # ---------------------------------------------------------------------------------- launch mirror
 def xcd_choose(dtype, GX, GY, gx, gy):
-    """xcd_choose (hmcx_mlp.hip:1759-1778): (xmap, xbx, xby) of a gx × gy tile plane in a GX × GY grid."""
+    """xcd_choose (hmcx_mlp.hip): (xmap, xbx, xby) of a gx × gy tile plane in a GX × GY grid."""
     if dtype != "float32" or gx * gy < 16 or (GX * GY) % 8:
         return 0, 0, 0
     per = GX * GY // 8
@@ -57,7 +58,7 @@ def xcd_choose(dtype, GX, GY, gx, gy):
 
 
 def k_split(K):
-    """mm_body (hmcx_mlp.hip:588-624): Kq = the k range per wave (a multiple of 16); ``chunks`` the number of
+    """mm_body's K split (hmcx_mlp_kernels.h): Kq = the k range per wave (a multiple of 16); ``chunks`` the number of
     16-wide chunks of each of the eight waves — 1 to 3 fill the register ring, 4, 5 and 6 reload slot 0, 1
     and 2 (at +48 / +64 / +80), 7 and 8 go round again — and 0 for a wave with no K at all."""
     Kq = (K + 16 * MM_NW - 1) // (16 * MM_NW) * 16
@@ -70,15 +71,15 @@ def k_split(K):
 
 
 def mm(name, epi, dtype, M, N, K, TA, TB, h1_a=False, vec_masks=True, placed=False, mk="none"):
-    """mm() (hmcx_mlp.hip:1780-1822) for operands whose base pointers are 16-byte aligned (device
+    """mm() (hmcx_mlp.hip) for operands whose base pointers are 16-byte aligned (device
     allocations and workspace blocks are): the launch signature of one k_mm."""
     V = 4 if dtype == "float32" else 2
     lda, ldb = (M if TA else K), (K if TB else N)
     kvec = K % V == 0
-    av = (not TA) and (not h1_a or vec_masks) and kvec and lda % V == 0          # :1791-1798
-    bv = bool(TB) and kvec and ldb % V == 0                                       # :1799
-    gx, gy = (M + 31) // 32, (N + 31) // 32                                       # :1788
-    xmap = xcd_choose(dtype, gx, gy, gx, gy) if placed else (0, 0, 0)             # :1790 (MM_STORE / MM_UPD)
+    av = (not TA) and (not h1_a or vec_masks) and kvec and lda % V == 0          # mm(): h1ok, kvec, aal
+    bv = bool(TB) and kvec and ldb % V == 0                                       # mm(): bv
+    gx, gy = (M + 31) // 32, (N + 31) // 32                                       # mm(): grid
+    xmap = xcd_choose(dtype, gx, gy, gx, gy) if placed else (0, 0, 0)             # mm(): MM_STORE / MM_UPD
     Kq, chunks = k_split(K)
     return dict(name=name, epi=epi, av=av, bv=bv, xmap=xmap[0], block=xmap[1:], Kq=Kq, chunks=chunks,
                 empty_wave=0 in chunks, ragged_m=M % 32 != 0, ragged_n=N % 32 != 0, ragged_k=K % 16 != 0,
@@ -86,7 +87,7 @@ def mm(name, epi, dtype, M, N, K, TA, TB, h1_a=False, vec_masks=True, placed=Fal
 
 
 def l3_rows(nt, nj):
-    """l3_backward (hmcx_mlp.hip:421-467) for a slice of nj columns: R row groups, RB rows per pass and the
+    """l3_backward (hmcx_mlp_kernels.h) for a slice of nj columns: R row groups, RB rows per pass and the
     number of ``jb`` passes over the slice."""
     R = max(1, nt // nj)
     cols = nt // R
@@ -95,9 +96,9 @@ def l3_rows(nt, nj):
 
 
 def layer3(dtype, B, n_mid, n_out, backward):
-    """mlp_forward's narrow / wide choice (hmcx_mlp.hip:1884-1900), the MM_L3CE slice count (:1789, :684-685)
-    and the ``wl`` test (:401; scratch of the narrow kernel (MM_NW − 1)·32·33 values, :686; of the wide one
-    MM_NT, :900)."""
+    """mlp_forward's narrow / wide choice (hmcx_mlp.hip), the MM_L3CE slice count (mm()'s grid.y; mm_body's column
+    slices, hmcx_mlp_kernels.h) and the ``wl`` test (l3_backward; scratch of the narrow kernel (MM_NW − 1)·32·33
+    values, mm_body's MM_L3CE epilogue; of the wide one MM_NT, k_l3_wide)."""
     if n_out <= 32:
         gy = max(1, min(8, n_mid // 32))
         cw = -(-n_mid // gy)
@@ -114,24 +115,24 @@ def layer3(dtype, B, n_mid, n_out, backward):
 
 
 def launches(B, n_in, n_mid, n_out, dtype, masks="vals", aligned=True):
-    """The launches of hmcx_mlp_grad (mlp_grad_t, hmcx_mlp.hip:2413-2441) followed by those hmcx_mlp_loss adds
-    when it returns logits (mlp_loss_t, :2751-2772): a list of mm() signatures, the layer-3 one under 'l3'.
+    """The launches of hmcx_mlp_grad (mlp_grad_t → mlp_grad_launch, hmcx_mlp.hip) followed by those hmcx_mlp_loss adds
+    when it returns logits (mlp_loss_t): a list of mm() signatures, the layer-3 one under 'l3'.
     masks 'vals' (a [3][B][n_mid] buffer; ``aligned``: on a 16-byte boundary) or 'none' (NULL)."""
     mk = masks
-    vec_masks = n_mid % 4 == 0 and (aligned or masks == "none")                   # net_init :1716, oneoff_net :2379
-    out = [mm("layer1", "STORE", dtype, B, n_mid, n_in, 0, 1, placed=True),      # mlp_forward :1840-1845
-           mm("layer2", "L2", dtype, B, n_mid, n_mid, 0, 1, h1_a=True, vec_masks=vec_masks, mk=mk)]   # :1865-1870
+    vec_masks = n_mid % 4 == 0 and (aligned or masks == "none")                   # net_init, oneoff_net
+    out = [mm("layer1", "STORE", dtype, B, n_mid, n_in, 0, 1, placed=True),      # mlp_forward: xw
+           mm("layer2", "L2", dtype, B, n_mid, n_mid, 0, 1, h1_a=True, vec_masks=vec_masks, mk=mk)]   # mlp_forward: h2, d3
     l3 = layer3(dtype, B, n_mid, n_out, True)
     if l3["kind"] == "narrow":
-        g = mm("layer3", "L3CE", dtype, B, n_out, n_mid, 0, 1, mk=mk)            # :1884-1887
+        g = mm("layer3", "L3CE", dtype, B, n_out, n_mid, 0, 1, mk=mk)            # mlp_forward: n_out ≤ 32
     else:
-        g = mm("layer3", "STORE", dtype, B, n_out, n_mid, 0, 1, placed=True)     # :1888-1892, then k_l3_wide
+        g = mm("layer3", "STORE", dtype, B, n_out, n_mid, 0, 1, placed=True)     # mlp_forward: d3·W3ᵀ, then k_l3_wide
     g["l3"] = l3
     out.append(g)
-    out.append(mm("ga1", "GA1", dtype, B, n_mid, n_mid, 0, 0, mk=mk))            # mlp_ga1 :1903-1910
-    out.append(mm("gW1", "UPD", dtype, n_mid, n_in, B, 1, 0, placed=True))       # wgrad_build :1923
-    out.append(mm("gW2", "UPD", dtype, n_mid, n_mid, B, 1, 0, placed=True, mk=mk))   # :1920 (B operand OP_H1)
-    out.append(mm("logits", "STORE", dtype, B, n_out, n_mid, 0, 1, placed=True))     # mlp_forward :1871-1875
+    out.append(mm("ga1", "GA1", dtype, B, n_mid, n_mid, 0, 0, mk=mk))            # mlp_ga1
+    out.append(mm("gW1", "UPD", dtype, n_mid, n_in, B, 1, 0, placed=True))       # wgrad_build, v = 0
+    out.append(mm("gW2", "UPD", dtype, n_mid, n_mid, B, 1, 0, placed=True, mk=mk))   # v = 2 (B operand OP_H1)
+    out.append(mm("logits", "STORE", dtype, B, n_out, n_mid, 0, 1, placed=True))     # mlp_forward: logits
     return out
 
 

@@ -384,7 +384,7 @@ def _philox_host(c0, c1, c2, c3, seed):
 
 
 def _keep_group_host(seed, n3, slot, step, chain):
-    """Host twin of hmcx_mlp.hip::keep_group, written from its definition (per-byte compares, not the
+    """Host twin of hmcx_mlp_mask.h::keep_group, written from its definition (per-byte compares, not the
     kernel's SWAR form): the keep flags of elements 0 … n3 − 1 of one forward."""
     nG = (n3 + 63) // 64
     G = np.arange(nG, dtype=np.uint64)

@@ -20,9 +20,10 @@ def test_case_table_reaches_every_launch_branch():
 
 
 def test_mirror_on_known_launches():
-    """The mirror against facts stated in csrc/hmcx_mlp.hip and DESIGN 5.3 for config 3 (784-256-256-10,
-    B = 500, float32): the W1 gradient's 8 x 25 tile plane takes the y-major chunks, 6880 = the largest
-    n_out·n_mid with W3 staged in LDS, float64 never leaves the dispatch order."""
+    """The mirror against facts stated in csrc/hmcx_mlp.hip (xcd_choose), csrc/hmcx_mlp_kernels.h (l3_backward)
+    and DESIGN 5.3 for config 3 (784-256-256-10, B = 500, float32): the W1 gradient's 8 x 25 tile plane takes
+    the y-major chunks, 6880 = the largest n_out·n_mid with W3 staged in LDS, float64 never leaves the dispatch
+    order."""
     g = {s["name"]: s for s in mc.launches(500, 784, 256, 10, "float32")}
     assert g["gW1"]["tiles"] == (8, 25) and g["gW1"]["xmap"] == 1
     assert g["layer1"]["Kq"] == 112 and g["layer2"]["Kq"] == 32 and g["gW2"]["Kq"] == 64

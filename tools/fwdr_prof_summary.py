@@ -1,4 +1,4 @@
-"""Summarise HMCX_FWDR_PROF stamps (hmcx_mlp.hip k_fwdr): per phase, the median over launches of the
+"""Summarise HMCX_FWDR_PROF stamps (hmcx_mlp_kernels.h k_fwdr): per phase, the median over launches of the
 median / max over workgroups of (stamp − the launch's first workgroup start), in µs (s_memrealtime,
 100 MHz).  Usage: python tools/fwdr_prof_summary.py <file>"""
 import sys

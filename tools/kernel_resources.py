@@ -5,7 +5,9 @@ Reads the clang offload bundles of the library's .hip_fatbin section (one per co
 each gfx950 code object and prints, from its AMDHSA metadata note (llvm-readelf --notes), every
 kernel's VGPR / AGPR / SGPR counts, spill counts and private segment (scratch) size.  A kernel that
 spills to scratch is slow by an order of magnitude (round 5: a k_wgrad edit went from 160 VGPRs to 2,264
-spilled ones, 20.6 → 175 µs per step), so `--check` exits non-zero when any kernel has scratch.
+spilled ones, 20.6 → 175 µs per step), so `--check` exits non-zero when any kernel has scratch.  A kernel that
+sits in more than one code object is listed once in the table (its first copy) and again after it, with the
+number of copies.
 
     python tools/kernel_resources.py [lib.so] [--check] [--grep REGEX]
 """
@@ -79,10 +81,12 @@ def main():
     pat = None
     if "--grep" in sys.argv:
         pat = re.compile(sys.argv[sys.argv.index("--grep") + 1])
-    ks = {}
+    ks, copies = {}, {}
     for co in code_objects(fatbin(lib)):
         for k in kernels(co):
-            ks[k["symbol"][:-3]] = k
+            sym = k["symbol"][:-3]
+            copies[sym] = copies.get(sym, 0) + 1
+            ks.setdefault(sym, k)           # the table shows the first copy; the others are reported below
     names = sorted(ks)
     bad = 0
     for sym, dn in zip(names, demangle(names)):
@@ -96,6 +100,9 @@ def main():
             dn[:90], k.get("vgpr_count"), k.get("agpr_count", "0"), k.get("sgpr_count"), k.get("vgpr_spill_count", "0"),
             k.get("sgpr_spill_count", "0"), scratch, k.get("group_segment_fixed_size", "?"), flag))
     print("%d kernels, %d with scratch" % (len(names), bad))
+    dup = sorted(s for s in names if copies[s] > 1)
+    for sym, dn in zip(dup, demangle(dup)):
+        print("in %d code objects: %s" % (copies[sym], dn[:120]))
     if "--check" in sys.argv and bad:
         sys.exit(1)
 

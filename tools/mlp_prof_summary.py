@@ -1,4 +1,4 @@
-"""Summarise HMCX_MLP_PROF stamps (hmcx_mlp.hip MM_L23): per phase, the median over launches of
+"""Summarise HMCX_MLP_PROF stamps (hmcx_mlp_kernels.h MM_L23): per phase, the median over launches of
 the median / max over workgroups of (stamp − the workgroup's first stamp), in µs (s_memrealtime,
 100 MHz).  Usage: python tools/mlp_prof_summary.py <file>"""
 import sys

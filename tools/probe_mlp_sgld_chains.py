@@ -22,7 +22,7 @@ from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import mlp  #
 from dropout_hamiltonian_montecarlo_amd.hamiltonian.inference.gpu.sgld import sgld  # noqa: E402
 
 N, B, SHAPE, EPS = 60000, 500, (784, 256, 10), 1e-3
-GROUP = 6                                     # chains per launch group (MAXPROB of csrc/hmcx_mlp.hip)
+GROUP = 6                                     # chains per launch group (MAXPROB of csrc/hmcx_mlp_kernels.h)
 
 
 def main():

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Recompile the named units of __graft_entry__.UNITS (by source file) and relink lib/libhmcx.so.
-    python tools/rebuild_units.py hmcx_mlp.hip [hmcx_wide.hip ...]"""
+    python tools/rebuild_units.py hmcx_mlp.hip [hmcx_wide.hip ...]
+After an edit to a header, name every source that includes it (hmcx_mlp_kernels.h: hmcx_mlp.hip hmcx_mlp_chains.hip)."""
 import os
 import subprocess
 import sys
