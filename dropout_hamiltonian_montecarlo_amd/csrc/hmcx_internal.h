@@ -142,7 +142,9 @@ struct Tiling {
 };
 Tiling make_tiling(int B, int D, int K, int C);
 
-enum FwdMode { FWD_GRAD = 0, FWD_SGHMC = 1, FWD_LL = 2, FWD_PRED = 3 };
+// FWD_PREDZ: FWD_PRED that stores the clipped logit z in place of the probability (the linear predictive's
+// float32 sigmoid statistics are taken from z in float64, hmcx_lin_pred.hip)
+enum FwdMode { FWD_GRAD = 0, FWD_SGHMC = 1, FWD_LL = 2, FWD_PRED = 3, FWD_PREDZ = 4 };
 // GRAD_SGLD_GPU: the CuPy file's SGLD update p = ν⊙p_prev − ½ε∇U, q += p (gpu/sgld.py:11-20, A2g)
 // GRAD_HMC: full-batch HMC sub-steps (cpu/hmc.py:49-54) fused into the gradient epilogue, per hmc_flags
 enum GradMode { GRAD_OUT = 0, GRAD_SGHMC = 1, GRAD_SGLD = 2, GRAD_SGD = 3, GRAD_SGLD_GPU = 4, GRAD_HMC = 5 };
@@ -245,7 +247,7 @@ template <typename T> int softmax_grad_t(hmcx_ctx*, const void*, const void*, in
 template <typename T> int softmax_loglik_t(hmcx_ctx*, const void*, const void*, int, int, int, int, const void*,
                                            const void*, double*, int link = LINK_SOFTMAX);
 template <typename T> int softmax_predict_t(hmcx_ctx*, const void*, int, int, int, int, const void*, const void*,
-                                            void*, int link = LINK_SOFTMAX);
+                                            void*, int link = LINK_SOFTMAX, bool logits = false);
 template <typename T> int sgd_run_t(hmcx_ctx*, const hmcx_sgd_args*);
 template <typename T> int sumsq_t(hmcx_ctx*, const void*, int64_t, double*);
 template <typename T> int sghmc_run_t(hmcx_ctx*, const hmcx_sampler_args*);

@@ -11,9 +11,10 @@
 // General path (every shape hmcx_softmax_predict accepts): draws in chunks.  Without dropout a chunk is up to
 // LG_CHUNK parameter sets, packed [D][chunk·K] (k_lpred_pack) for one k_fwd launch in FWD_PRED mode
 // (softmax_predict_t) into the chunk buffer; with dropout a chunk is one draw: k_lpred_xmask writes X ⊙ Z_d,
-// then k_fwd on W_s as it lies.  k_lpred_reduce — one thread per row, one wave per workgroup — adds p, H[p],
-// p[y] of the chunk's draws to the per-row float64 accumulators in draw order and leaves each draw's
-// per-workgroup −log-likelihood and hits; k_lpred_finish / k_lpred_draws end the call.
+// then k_fwd on W_s as it lies.  A float32 sigmoid call stores k_fwd's clipped logits instead (FWD_PREDZ) and the
+// sigmoid is taken in float64 from them, as on the fused path.  k_lpred_reduce — one thread per row, one wave
+// per workgroup — adds p, H[p], p[y] of the chunk's draws to the per-row float64 accumulators in draw order and
+// leaves each draw's per-workgroup −log-likelihood and hits; k_lpred_finish / k_lpred_draws end the call.
 //
 // Fused path (k_lpred_fused; eligibility: lpred_fused_shape_ok): a workgroup owns a 16-row block of X, staged
 // in LDS once, and a contiguous group of units.  A unit is what one wave carries through D in LF_NACC
@@ -98,7 +99,9 @@ __global__ __launch_bounds__(256) void k_lpred_xmask(const T* X, T* Xd, int64_t 
   Xd[i] = X[i] * (z ? T(1) : T(0));
 }
 
-// The probabilities prob [N][nc·K] of draws d0 … d0 + nc − 1 into the accumulators, in draw order.
+// The probabilities prob [N][nc·K] of draws d0 … d0 + nc − 1 into the accumulators, in draw order.  sig: 0 the
+// softmax link, 1 the sigmoid link on probabilities, 2 the sigmoid link on clipped logits (float32 calls: a
+// float32 probability is exactly 1 from z = 17.33 on, and log(1 − p) of it is −inf, 0·log 0 a NaN).
 // nll_part / corr_part [S·T][gridDim.x]: each draw's −log-likelihood and hits of this workgroup's rows.
 template <typename T>
 __global__ __launch_bounds__(LG_NT) void k_lpred_reduce(const T* prob, const int32_t* y, int N, int K, int nc, int d0,
@@ -117,7 +120,8 @@ __global__ __launch_bounds__(LG_NT) void k_lpred_reduce(const T* prob, const int
       double* am = acc_mean + (size_t)n * K;
       const bool first = d0 == 0 && c == 0;
       if (sig) {
-        const double pk = (double)p[0];
+        // sig == 2: the chunk holds the clipped logit and p is formed in float64, as the fused kernel does
+        const double pk = sig == 2 ? 1.0 / (1.0 + exp(-(double)p[0])) : (double)p[0];   // logistic.py:53-55
         am[0] = first ? pk : am[0] + pk;
         sig_stats(pk, yv, H, py, nll, hit);
       } else {
@@ -533,6 +537,9 @@ int lin_predictive_t(hmcx_ctx* ctx, const hmcx_linear_predictive_args* a) {
     }
     if ((rc = timing_begin(ctx, st))) return rc;               // after the buffers: nothing below fails on size
     const int link = sig ? LINK_SIGMOID : LINK_SOFTMAX;
+    // float32 sigmoid: the chunk buffer takes k_fwd's clipped logits, and k_lpred_reduce forms p in float64
+    // (the float64 call keeps the probability: it is the same double either way)
+    const bool zsig = sig && sizeof(T) == 4;
     for (int d0 = 0; d0 < DR; d0 += CH) {
       const int nc = std::min(CH, DR - d0);
       const T* Xc = X;
@@ -551,10 +558,10 @@ int lin_predictive_t(hmcx_ctx* ctx, const hmcx_linear_predictive_args* a) {
         HMCX_HIP(ctx, hipGetLastError());
         Ws = Wc;
       }
-      if ((rc = softmax_predict_t<T>(ctx, Xc, N, D, K, nc, Ws, b + (size_t)(d0 / Tn) * K, prob, link))) return rc;
+      if ((rc = softmax_predict_t<T>(ctx, Xc, N, D, K, nc, Ws, b + (size_t)(d0 / Tn) * K, prob, link, zsig))) return rc;
       if (want_rows || want_draws) {
-        hipLaunchKernelGGL(k_lpred_reduce<T>, dim3(nb), dim3(LG_NT), 0, st, (const T*)prob, a->y, N, K, nc, d0, sig, gm,
-                           gH, gpy, np, cp);
+        hipLaunchKernelGGL(k_lpred_reduce<T>, dim3(nb), dim3(LG_NT), 0, st, (const T*)prob, a->y, N, K, nc, d0,
+                           zsig ? 2 : sig, gm, gH, gpy, np, cp);
         HMCX_HIP(ctx, hipGetLastError());
       }
     }

@@ -87,7 +87,8 @@ __global__ __launch_bounds__(NW * 64) void k_fwd(FwdArgs<T> a) {
   for (int q = 0; q < YPT; ++q) {
     const int e = tid + q * NTH;
     const int i = e / NT, j = e - (e / NT) * NT;
-    yreg[q] = (mode != FWD_PRED && e < 16 * NT && i < nrow && j < ncols) ? a.Y[(size_t)(m0 + i) * K + j % K] : T(0);
+    const bool yok = mode != FWD_PRED && mode != FWD_PREDZ && e < 16 * NT && i < nrow && j < ncols;
+    yreg[q] = yok ? a.Y[(size_t)(m0 + i) * K + j % K] : T(0);
   }
 
   // ---- Z = X·W : wave w owns d in [w·Dw, (w+1)·Dw), 4 chunks of 16 loaded before their MFMAs
@@ -236,6 +237,7 @@ __global__ __launch_bounds__(NW * 64) void k_fwd(FwdArgs<T> a) {
     const size_t gidx = (size_t)(m0 + i) * a.N + n0 + j;
     const T yh = sig ? eA[i][j] : eA[i][j] / sA[i][cc];                   // softmax.py:35-36
     if (mode == FWD_PRED) { a.prob[gidx] = yh; continue; }
+    if (mode == FWD_PREDZ) { a.prob[gidx] = zA[i][j]; continue; }
     const T y = yt[i][j];
     if (mode == FWD_GRAD || sghmc) {
       const T d = y - yh;                                                 // softmax.py:52
@@ -843,9 +845,9 @@ int softmax_loglik_t(hmcx_ctx* ctx, const void* X, const void* Y, int B, int D, 
 
 template <typename T>
 int softmax_predict_t(hmcx_ctx* ctx, const void* X, int B, int D, int K, int C, const void* W, const void* b,
-                      void* prob, int link) {
+                      void* prob, int link, bool logits) {
   const Tiling t = make_tiling(B, D, K, C);
-  FwdArgs<T> f = fwd_args<T>(X, nullptr, W, b, B, D, K, C, t, FWD_PRED);
+  FwdArgs<T> f = fwd_args<T>(X, nullptr, W, b, B, D, K, C, t, logits ? FWD_PREDZ : FWD_PRED);
   f.link = link;
   f.prob = (T*)prob;
   HMCX_HIP(ctx, launch_fwd<T>(f, t, ctx->stream));
@@ -2009,9 +2011,9 @@ template int softmax_loglik_t<float>(hmcx_ctx*, const void*, const void*, int, i
 template int softmax_loglik_t<double>(hmcx_ctx*, const void*, const void*, int, int, int, int, const void*,
                                       const void*, double*, int);
 template int softmax_predict_t<float>(hmcx_ctx*, const void*, int, int, int, int, const void*, const void*, void*,
-                                      int);
+                                      int, bool);
 template int softmax_predict_t<double>(hmcx_ctx*, const void*, int, int, int, int, const void*, const void*, void*,
-                                       int);
+                                       int, bool);
 template int sgd_run_t<float>(hmcx_ctx*, const hmcx_sgd_args*);
 template int sgd_run_t<double>(hmcx_ctx*, const hmcx_sgd_args*);
 template int hmc_chains_run_t<float>(hmcx_ctx*, const hmcx_hmc_chains_args*);
