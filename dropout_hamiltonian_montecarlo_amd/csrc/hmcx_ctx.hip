@@ -1267,6 +1267,62 @@ int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a) 
   return a->dtype == HMCX_F64 ? mlp_sgld_chains_t<double>(ctx, a) : mlp_sgld_chains_t<float>(ctx, a);
 }
 
+int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a) {
+  HMCX_GUARD_CTX(ctx);
+  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
+  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
+  if (rc) return rc;
+  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_steps < 0");
+  if (a->C < 1 || a->C > 64) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: C must be 1 .. 64");
+  if ((uint64_t)a->chain0 + (uint64_t)a->C > 0x100000000ULL)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: chain0 + C wraps 2^32");
+  if ((uint64_t)a->step_base + (uint64_t)a->n_steps > 0x100000000ULL)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: step_base + n_steps wraps 2^32");
+  // the noise index of an element is a 32-bit Philox counter field: all six variables together stay below 2^31
+  if ((long long)a->n_mid * a->n_in + (long long)a->n_mid * a->n_mid + (long long)a->n_out * a->n_mid +
+          2LL * a->n_mid + a->n_out > 0x7fffffffLL)
+    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp hmc chains: more than 2^31 - 1 parameters");
+  if (!a->X || !a->y || !a->eps || !a->n_iter || !a->u_accept || !mlp_par_ok(&a->par) || !a->out_A || !a->out_accepted)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: null pointer");
+  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: bad noise_mode");
+  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: BUFFER noise mode needs noise and noise_off");
+  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
+      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: bad mask_mode");
+  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: FIXED masks need masks and mask_off");
+  if (a->want_eval && !a->out_eval_loss)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: want_eval needs out_eval_loss");
+  if (a->want_draw && !mlp_par_ok(&a->draws))
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: want_draw needs draws");
+  int seen = 0;
+  for (int i = 0; i < 6; ++i) {
+    const int v = a->order[i];
+    if (v < 0 || v > 5 || ((seen >> v) & 1))
+      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: order must be a permutation of 0..5");
+    seen |= 1 << v;
+  }
+  int64_t n_draws = 0;
+  for (int64_t j = 0; j < (int64_t)a->n_steps * a->C; ++j) {
+    if (a->n_iter[j] < 0) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_iter < 0");
+    // the mask slot of the step's last forward, 0x80000000 + 6n + 3, stays below 2^32
+    if ((int64_t)a->n_iter[j] > (0x7fffffffLL - 3) / 6)
+      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_iter so large that the forward number wraps 2^32");
+    if (a->noise_mode == HMCX_NOISE_BUFFER && a->noise_off[j] < 0)
+      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: negative noise_off");
+    if (a->mask_mode == HMCX_MLP_MASKS_FIXED && a->mask_off[j] < 0)
+      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: negative mask_off");
+  }
+  for (int s = 0; s < a->n_steps; ++s)
+    if (a->want_draw && a->want_draw[s]) ++n_draws;
+  if (n_draws > a->draw_stride)
+    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: draw_stride below the call's flagged steps");
+  if (a->n_steps == 0) return HMCX_OK;
+  return a->dtype == HMCX_F64 ? mlp_hmc_chains_t<double>(ctx, a) : mlp_hmc_chains_t<float>(ctx, a);
+}
+
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   HMCX_GUARD_CTX(ctx);
   if (!a) return set_error(ctx, HMCX_EINVAL, "null args");

@@ -1,7 +1,8 @@
 // hmcx_mlp_chains.hip — chains as problems on the dropout MLP (hmcx_mlp_sgld_chains_run): several SGLD chains on
 // shared minibatches run the one-chain schedule (mlp_sgld_t, hmcx_mlp.hip) with every launch widened over a group
 // of up to MAXPROB chains — k_mmc (k_mmb with a problem table that also carries the buffers a chain owns),
-// k_pending_chains, k_mlp_sgld_chains.
+// k_pending_chains, k_mlp_sgld_chains.  The group forward / gradient launches are helpers (mlp_chains_forward,
+// mlp_chains_backward) that the multi-chain HMC of hmcx_mlp_hmc_chains.hip calls as well.
 // A unit of its own, once per dtype, so that hmcx_mlp.hip's code objects keep the layout they were measured with
 // (DESIGN.md §5.3).  The launches shared with the one-chain paths (layer 1, the n_out > 32 forward, the mask draws)
 // go through helpers of hmcx_mlp.hip seen here as prototypes only (hmcx_mlp_shared.h, hmcx_internal.h): including
@@ -138,12 +139,12 @@ __global__ __launch_bounds__(256) void k_pending_chains(PendChains<T> a) {
 // Launch k_mmc for a group of chains: mm()'s choices — tile grid, vector paths (over every chain's operands), mask
 // kind (explicit values or none: the chains never read keep flags) — with one plane per chain and no pending plane.
 template <typename T, int EPI, int TA, int TB, int AOP = OP_PLAIN, int BOP = OP_PLAIN>
-hipError_t mmc(MlpNet<T>& net, MMArgs<T>& a, const MMChains<T>& pr) {
+hipError_t mmc(hipStream_t st, bool vec_masks, MMArgs<T>& a, const MMChains<T>& pr) {
   if (a.ta != TA || a.tb != TB || pr.n < 1 || pr.n > MAXPROB || a.ms.keep) return hipErrorInvalidValue;
   a.pend.n = 0;
   dim3 grid((a.M + 31) / 32, (a.N + 31) / 32, pr.n), blk(MM_NT);
   if (EPI == MM_L3CE) grid.y = (unsigned)std::max(1, std::min(8, a.n_mid / 32));   // n_mid column slices
-  const bool h1ok = AOP != OP_H1 || net.vec_masks;
+  const bool h1ok = AOP != OP_H1 || vec_masks;
   const bool kvec = a.K % (int)(16 / sizeof(T)) == 0;
   bool aal = true, bal = true;
   for (int p = 0; p < pr.n; ++p) {
@@ -152,7 +153,6 @@ hipError_t mmc(MlpNet<T>& net, MMArgs<T>& a, const MMChains<T>& pr) {
   }
   const bool av = !TA && h1ok && kvec && aal;
   const bool bv = TB && kvec && bal;
-  hipStream_t st = net.st;
   auto go = [&](auto mkc) {
     constexpr int MK = decltype(mkc)::value;
     if (av && bv) hipLaunchKernelGGL((k_mmc<T, EPI, AOP, BOP, TA, TB, !TA, TB, MK>), grid, blk, 0, st, a, pr);
@@ -168,6 +168,113 @@ hipError_t mmc(MlpNet<T>& net, MMArgs<T>& a, const MMChains<T>& pr) {
     go(std::integral_constant<int, MK_NONE>{});
   }
   return hipGetLastError();
+}
+
+// The group forward / gradient launches (hmcx_mlp_shared.h), shared by the multi-chain SGLD below and the multi-chain
+// HMC of hmcx_mlp_hmc_chains.hip, which sees them as prototypes.
+template <typename T> static bool list_vec_masks(const ChainList<T>& L) {
+  bool v = true;
+  for (int c = 0; c < L.n; ++c) v = v && L.net[c]->vec_masks;
+  return v;
+}
+template <typename T>
+__attribute__((used)) int mlp_chains_forward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, bool layer1) {
+  MlpNet<T>& net = *L.net[0];
+  const int np = L.n, B = net.B, nm = net.n_mid, n_out = net.n_out;
+  if (np < 1 || np > MAXPROB) return set_error(ctx, HMCX_EINVAL, "mlp chains: bad chain list");
+  const L3Want w{(want & 15u) != 0, (want & 8u) != 0, (want & 32u) != 0, (want & 16u) != 0};
+  if (layer1) {
+    const T* W1[MAXPROB];
+    T* xw[MAXPROB];
+    for (int c = 0; c < np; ++c) { W1[c] = L.q[c][0]; xw[c] = L.net[c]->xw; }
+    HMCX_HIP(ctx, mlp_layer1_batch<T>(net, W1, xw, np));
+  }
+  if (n_out > 32) {
+    for (int c = 0; c < np; ++c) {
+      L.net[c]->xw_valid = true;
+      HMCX_HIP(ctx, mlp_forward<T>(*L.net[c], L.q[c], L.ms[c], L.lpart[c], w));
+    }
+    return HMCX_OK;
+  }
+  const bool vm = list_vec_masks(L);
+  MMChains<T> pr{};
+  pr.n = np;
+  for (int c = 0; c < np; ++c) {
+    MMProbC<T>& p = pr.p[c];
+    p.A = L.net[c]->xw; p.B = L.q[c][2]; p.C = L.net[c]->h2; p.C2 = L.net[c]->d3;
+    p.b1 = L.q[c][1]; p.bias = L.q[c][3]; p.ms = L.ms[c];
+  }
+  MMArgs<T> a{};
+  mm_set<T>(a, B, nm, nm, net.xw, nm, 0, L.q[0][2], nm, 1, net.h2, nm);
+  a.ms = L.ms[0];
+  HMCX_HIP(ctx, (mmc<T, MM_L2, 0, 1, OP_H1>(net.st, vm, a, pr)));
+  pr = MMChains<T>{};
+  pr.n = np;
+  for (int c = 0; c < np; ++c) {
+    MMProbC<T>& p = pr.p[c];
+    const MlpNet<T>& cn = *L.net[c];
+    p.A = cn.d3; p.B = L.q[c][4]; p.C = cn.gz; p.bias = L.q[c][5]; p.ms = L.ms[c];
+    p.lpart = L.lpart[c];
+    p.W3 = L.q[c][4]; p.h2 = cn.h2; p.d3 = cn.d3;
+    p.ga2 = w.ga2 ? cn.ga2 : nullptr;
+    p.pb2 = w.pb2 ? cn.pb2 : nullptr;
+    p.pb3 = w.pb3 ? cn.pb3 : nullptr;
+    p.pw3 = w.pw3 ? cn.pw3 : nullptr;
+  }
+  a = MMArgs<T>{};
+  mm_set<T>(a, B, n_out, nm, net.d3, nm, 0, L.q[0][4], nm, 1, net.gz, n_out);
+  a.y = net.y; a.n_mid = nm; a.ms = L.ms[0];
+  HMCX_HIP(ctx, (mmc<T, MM_L3CE, 0, 1>(net.st, vm, a, pr)));
+  return HMCX_OK;
+}
+
+template <typename T>
+__attribute__((used)) int mlp_chains_backward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, double alpha) {
+  MlpNet<T>& net = *L.net[0];
+  const int np = L.n, B = net.B, nm = net.n_mid;
+  if (np < 1 || np > MAXPROB) return set_error(ctx, HMCX_EINVAL, "mlp chains: bad chain list");
+  const bool vm = list_vec_masks(L);
+  MMChains<T> pr{};
+  MMArgs<T> a{};
+  if (want & 3u) {
+    pr.n = np;
+    for (int c = 0; c < np; ++c) {                           // layer-1 backward (+ b1 partials)
+      MMProbC<T>& p = pr.p[c];
+      const MlpNet<T>& cn = *L.net[c];
+      p.A = cn.ga2; p.B = L.q[c][2]; p.C = cn.ga1; p.b1 = L.q[c][1]; p.ms = L.ms[c];
+      p.colpart = cn.pb1; p.H = cn.xw;
+    }
+    mm_set<T>(a, B, nm, nm, net.ga2, nm, 0, L.q[0][2], nm, 0, net.ga1, nm);
+    a.ms = L.ms[0];
+    HMCX_HIP(ctx, (mmc<T, MM_GA1, 0, 0>(net.st, vm, a, pr)));
+  }
+  if (want & 1u) {
+    pr = MMChains<T>{};
+    pr.n = np;
+    for (int c = 0; c < np; ++c) {                           // W1 gradient: ga1ᵀ·X
+      MMProbC<T>& p = pr.p[c];
+      p.A = L.net[c]->ga1; p.B = net.X; p.uW = L.q[c][0]; p.uG = L.g[c][0];
+    }
+    a = MMArgs<T>{};
+    mm_set<T>(a, nm, net.n_in, B, net.ga1, nm, 1, net.X, net.n_in, 0, nullptr, net.n_in);
+    a.upd_mode = UPD_GRAD; a.u.half_alpha = (T)(0.5 * alpha);
+    HMCX_HIP(ctx, (mmc<T, MM_UPD, 1, 0>(net.st, vm, a, pr)));
+  }
+  if (want & 4u) {
+    pr = MMChains<T>{};
+    pr.n = np;
+    for (int c = 0; c < np; ++c) {                           // W2 gradient: ga2ᵀ·h1, h1 from xw, b1 and m0
+      MMProbC<T>& p = pr.p[c];
+      p.A = L.net[c]->ga2; p.B = L.net[c]->xw; p.b1 = L.q[c][1]; p.ms = L.ms[c];
+      p.uW = L.q[c][2]; p.uG = L.g[c][2];
+    }
+    a = MMArgs<T>{};
+    mm_set<T>(a, nm, nm, B, net.ga2, nm, 1, net.xw, nm, 0, nullptr, nm);
+    a.ms = L.ms[0];
+    a.upd_mode = UPD_GRAD; a.u.half_alpha = (T)(0.5 * alpha);
+    HMCX_HIP(ctx, (mmc<T, MM_UPD, 1, 0, OP_PLAIN, OP_H1>(net.st, vm, a, pr)));
+  }
+  return HMCX_OK;
 }
 
 // SGLD of hmcx_mlp_sgld_chains_run: mlp_sgld_t's schedule with the chains as the problems of batched launches.
@@ -222,12 +329,15 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
   for (int c0 = 0; c0 < C; c0 += MAXPROB) {
     const int np = std::min(MAXPROB, C - c0);
     T* q[MAXPROB][6];
-    const T* W1[MAXPROB];
-    T* xw[MAXPROB];
+    T* gc[MAXPROB][6];
+    ChainList<T> L{};
+    L.n = np;
     for (int c = 0; c < np; ++c) {
-      for (int v = 0; v < 6; ++v) q[c][v] = (T*)s->par.p[v] + (size_t)(c0 + c) * (size_t)net.nvar(v);
-      W1[c] = q[c][0];
-      xw[c] = cn[c].xw;
+      for (int v = 0; v < 6; ++v) {
+        q[c][v] = (T*)s->par.p[v] + (size_t)(c0 + c) * (size_t)net.nvar(v);
+        gc[c][v] = g[v] + (size_t)c * net.nvar(v);
+      }
+      L.net[c] = &cn[c]; L.q[c] = q[c]; L.g[c] = gc[c]; L.lpart[c] = lpart + (size_t)c * nlb;
     }
     MlpSgld<T> k{};
     for (int v = 0; v < 6; ++v) {
@@ -246,7 +356,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
     const SgldStrides cs{s->draw_stride, (int64_t)mstride};
     // the masks of a forward: FIXED at `off` of the caller's buffer (every chain's), PHILOX the chain's part of
     // `scr`, NONE nothing
-    MaskSrc<T> ms[MAXPROB];
+    MaskSrc<T>* const ms = L.ms;
     auto masks_of = [&](int64_t off, const T* scr) {
       for (int c = 0; c < np; ++c) {
         const T* m = fixed ? (const T*)s->masks + off : philox ? scr + c * mstride : nullptr;
@@ -254,45 +364,8 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
         cn[c].vec_masks = n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
       }
     };
-    // the group's forward at its chains' θ: layer 1 as one batched launch, then layers 2 and 3
-    auto forward = [&](bool want) -> int {
-      HMCX_HIP(ctx, mlp_layer1_batch<T>(net, W1, xw, np));
-      if (n_out > 32) {
-        for (int c = 0; c < np; ++c) {
-          cn[c].xw_valid = true;
-          HMCX_HIP(ctx, mlp_forward<T>(cn[c], q[c], ms[c], lpart + (size_t)c * nlb, L3Want{want, want, want, want}));
-        }
-        return HMCX_OK;
-      }
-      MMChains<T> pr{};
-      pr.n = np;
-      for (int c = 0; c < np; ++c) {
-        MMProbC<T>& p = pr.p[c];
-        p.A = cn[c].xw; p.B = q[c][2]; p.C = cn[c].h2; p.C2 = cn[c].d3;
-        p.b1 = q[c][1]; p.bias = q[c][3]; p.ms = ms[c];
-      }
-      MMArgs<T> a{};
-      mm_set<T>(a, B, nm, nm, cn[0].xw, nm, 0, q[0][2], nm, 1, cn[0].h2, nm);
-      a.ms = ms[0];
-      HMCX_HIP(ctx, (mmc<T, MM_L2, 0, 1, OP_H1>(net, a, pr)));
-      pr = MMChains<T>{};
-      pr.n = np;
-      for (int c = 0; c < np; ++c) {
-        MMProbC<T>& p = pr.p[c];
-        p.A = cn[c].d3; p.B = q[c][4]; p.C = cn[c].gz; p.bias = q[c][5]; p.ms = ms[c];
-        p.lpart = lpart + (size_t)c * nlb;
-        p.W3 = q[c][4]; p.h2 = cn[c].h2; p.d3 = cn[c].d3;
-        p.ga2 = want ? cn[c].ga2 : nullptr;
-        p.pb2 = want ? cn[c].pb2 : nullptr;
-        p.pb3 = want ? cn[c].pb3 : nullptr;
-        p.pw3 = want ? cn[c].pw3 : nullptr;
-      }
-      a = MMArgs<T>{};
-      mm_set<T>(a, B, n_out, nm, cn[0].d3, nm, 0, q[0][4], nm, 1, cn[0].gz, n_out);
-      a.y = net.y; a.n_mid = nm; a.ms = ms[0];
-      HMCX_HIP(ctx, (mmc<T, MM_L3CE, 0, 1>(net, a, pr)));
-      return HMCX_OK;
-    };
+    // the group's forward at its chains' θ (want: with the layer-3 backward pieces of the gradient)
+    auto forward = [&](bool want) -> int { return mlp_chains_forward<T>(ctx, L, want ? 63u : 0u, true); };
     if (philox)
       for (int c = 0; c < np; ++c)
         if (int rc = mlp_masks_t<T>(ctx, B, n_mid, s->seed, s->chain0 + (uint32_t)(c0 + c), s->step_base, MASK_SLOT0,
@@ -306,39 +379,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
       }
       masks_of(fixed ? s->mask_off[si] : 0, mscr);
       if (int rc = forward(true)) return rc;
-      MMChains<T> pr{};
-      MMArgs<T> a{};
-      pr.n = np;
-      for (int c = 0; c < np; ++c) {                           // layer-1 backward (+ b1 partials)
-        MMProbC<T>& p = pr.p[c];
-        p.A = cn[c].ga2; p.B = q[c][2]; p.C = cn[c].ga1; p.b1 = q[c][1]; p.ms = ms[c];
-        p.colpart = cn[c].pb1; p.H = cn[c].xw;
-      }
-      mm_set<T>(a, B, nm, nm, cn[0].ga2, nm, 0, q[0][2], nm, 0, cn[0].ga1, nm);
-      a.ms = ms[0];
-      HMCX_HIP(ctx, (mmc<T, MM_GA1, 0, 0>(net, a, pr)));
-      pr = MMChains<T>{};
-      pr.n = np;
-      for (int c = 0; c < np; ++c) {                           // W1 gradient: ga1ᵀ·X
-        MMProbC<T>& p = pr.p[c];
-        p.A = cn[c].ga1; p.B = net.X; p.uW = q[c][0]; p.uG = g[0] + (size_t)c * net.nvar(0);
-      }
-      a = MMArgs<T>{};
-      mm_set<T>(a, nm, s->n_in, B, cn[0].ga1, nm, 1, net.X, s->n_in, 0, nullptr, s->n_in);
-      a.upd_mode = UPD_GRAD; a.u.half_alpha = (T)(0.5 * s->alpha);
-      HMCX_HIP(ctx, (mmc<T, MM_UPD, 1, 0>(net, a, pr)));
-      pr = MMChains<T>{};
-      pr.n = np;
-      for (int c = 0; c < np; ++c) {                           // W2 gradient: ga2ᵀ·h1, h1 from xw, b1 and m0
-        MMProbC<T>& p = pr.p[c];
-        p.A = cn[c].ga2; p.B = cn[c].xw; p.b1 = q[c][1]; p.ms = ms[c];
-        p.uW = q[c][2]; p.uG = g[2] + (size_t)c * net.nvar(2);
-      }
-      a = MMArgs<T>{};
-      mm_set<T>(a, nm, nm, B, cn[0].ga2, nm, 1, cn[0].xw, nm, 0, nullptr, nm);
-      a.ms = ms[0];
-      a.upd_mode = UPD_GRAD; a.u.half_alpha = (T)(0.5 * s->alpha);
-      HMCX_HIP(ctx, (mmc<T, MM_UPD, 1, 0, OP_PLAIN, OP_H1>(net, a, pr)));
+      if (int rc = mlp_chains_backward<T>(ctx, L, 63u, s->alpha)) return rc;
       PendChains<T> pc{};                                      // the bias / W3 gradients from the row-block partials
       pc.nparts = nlb; pc.half_alpha = (T)(0.5 * s->alpha); pc.pstride = pstride;
       {
@@ -399,8 +440,12 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
 
 #if !defined(HMCX_MLP_DTYPES) || (HMCX_MLP_DTYPES & 1)   // bit 0 float, bit 1 double, as hmcx_mlp.hip
 template int mlp_sgld_chains_t<float>(hmcx_ctx*, const hmcx_mlp_sgld_chains_args*);
+template int mlp_chains_forward<float>(hmcx_ctx*, ChainList<float>&, unsigned, bool);
+template int mlp_chains_backward<float>(hmcx_ctx*, ChainList<float>&, unsigned, double);
 #endif
 #if !defined(HMCX_MLP_DTYPES) || (HMCX_MLP_DTYPES & 2)
 template int mlp_sgld_chains_t<double>(hmcx_ctx*, const hmcx_mlp_sgld_chains_args*);
+template int mlp_chains_forward<double>(hmcx_ctx*, ChainList<double>&, unsigned, bool);
+template int mlp_chains_backward<double>(hmcx_ctx*, ChainList<double>&, unsigned, double);
 #endif
 }  // namespace hmcx

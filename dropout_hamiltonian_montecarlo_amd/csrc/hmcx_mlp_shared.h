@@ -1,6 +1,7 @@
 // hmcx_mlp_shared.h — the rest of what the MLP's compile units share, behind hmcx_mlp_kernels.h: the SGD / SGLD
 // update kernels, the net of one forward / backward (MlpNet) and prototypes of the launch helpers that hmcx_mlp.hip
-// defines.  A unit that sees only the prototypes (hmcx_mlp_chains.hip) instantiates none of the kernels they launch.
+// defines.  A unit that sees only the prototypes (hmcx_mlp_chains.hip, hmcx_mlp_hmc_chains.hip) instantiates none of
+// the kernels they launch.
 // hmcx_mlp.hip includes it behind its own static kernels: those are emitted in definition order.
 #pragma once
 #include "hmcx_mlp_kernels.h"
@@ -218,4 +219,24 @@ template <typename T> void mlp_workspace(Workspace& ws, MlpNet<T>& net);
 template <typename T> hipError_t mlp_layer1_batch(MlpNet<T>& net, const T* const* W1, T* const* out, int np);
 template <typename T>
 hipError_t mlp_forward(MlpNet<T>& net, T* const* q, const MaskSrc<T>& ms, double* lpart, L3Want w, T* logits = nullptr);
+
+// hmcx_mlp_chains.hip: a list of chains as the problems of batched launches (k_mmc).  Entry j is one chain: its net
+// (every buffer of a forward / backward is the chain's own; X, y and the dimensions are read from net[0]), its θ
+// and gradient outputs (six pointers each, canonical order), the masks of the forward and its loss partials.  The
+// list need not be dense in the caller's chains: a chain that has nothing to do is left out and writes nothing.
+template <typename T> struct ChainList {
+  int n;                              // 1 .. MAXPROB
+  MlpNet<T>* net[MAXPROB];
+  T* const* q[MAXPROB];
+  T* const* g[MAXPROB];
+  MaskSrc<T> ms[MAXPROB];
+  double* lpart[MAXPROB];
+};
+// The forward of every listed chain at its θ: layer 1 (`layer1`: one batched launch into the chains' xw), then
+// layers 2 and 3 with the layer-3 backward pieces the gradient components `want` (bit v) use — two k_mmc launches
+// (n_out ≤ 32) or mlp_forward chain by chain.  Then the rest of the gradient: layer-1 backward (want & 3), the W1
+// (bit 0) and W2 (bit 2) gradients into g; the bias / W3 gradients stay as the chains' row-block partials
+// (pb1, pb2, pw3, pb3) for the caller's element-wise kernel.  mlp_grad_launch's launches and flags per chain.
+template <typename T> int mlp_chains_forward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, bool layer1);
+template <typename T> int mlp_chains_backward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, double alpha);
 }  // namespace hmcx

@@ -778,6 +778,85 @@ typedef struct hmcx_mlp_sgld_chains_args {
 } hmcx_mlp_sgld_chains_args;
 int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a);
 
+/* Full-batch HMC on the MLP, n_steps steps of C chains in one call (extension; the reference's hmc.sample drives
+ * one chain step by step from the host): replaces hamiltonian/inference/cpu/hmc.py:39-64 (step, accept) over
+ * models/gpu/mlp.py for every (step s, chain c), with ε = eps[s], n = n_iter[s·C + c], u = u_accept[s·C + c]:
+ *   1. momentum: p = P standard normals laid out variable after variable in `order` (element e = the variable's
+ *      offset in that layout + its index).  HMCX_NOISE_BUFFER: noise[noise_off[s·C + c] + e] (double, converted
+ *      to dtype); HMCX_NOISE_PHILOX: the Philox normal of (seed, chain0 + c, step_base + s, slot 0, e) in dtype,
+ *      the stream hmcx_philox_normals / hmcx_philox_normals_f64 return on the host.
+ *   2. trajectory on copies (q', p'), exactly hmcx_mlp_hmc_leapfrog's: 1 + 6n gradient calls, kicks and drifts by
+ *      k_mlp_kicks's per-element arithmetic, each call computing only the components the next kicks read, the
+ *      layer-1 output reused until W1 moves.  The final p = −p is skipped: p is discarded after the step and the
+ *      sign does not change the kinetic energy.
+ *   3. the forwards of (s, c) are numbered in call order: f = 0 the gradient at q; f = 1 + 6·it + i the gradient
+ *      after the drift of order[i] in iteration it; f = 6n + 1 the proposal's energy forward; f = 6n + 2 the
+ *      current state's (hmc.py:68-69 evaluates the proposal first); f = 6n + 3 the record forward, only where
+ *      want_eval[s] is set.  Masks of forward f: HMCX_MLP_MASKS_NONE no dropout; FIXED masks +
+ *      mask_off[s·C + c] + f·3·B·n_mid (dtype; each chain its own block); PHILOX what hmcx_mlp_masks(seed,
+ *      chain0 + c, step_base + s, 0x80000000 + f) writes.
+ *   4. n = 0 keeps the numbering; its f = 0 gradient is never read and is not launched.  A still comes from the two
+ *      energy forwards: under dropout it is not 1.
+ *   5. energies: E = (loss + log_prior) + K, loss the mean CE of the forward (hmcx_mlp_loss's value up to the
+ *      order of the row-block sum), log_prior = −Σ_v ½·alpha·Σθ_v²/dim_v and K = Σ_v ½·Σp_v², both over `order`, in
+ *      float64 with a fixed summation order (hmcx_mlp_sghmc_run's composition).
+ *   6. A = min(1, exp(E_cur − E_new)) as Python's min (NaN gives 1); accepted = isfinite(A) && u < A; an
+ *      accepted step commits q' to par.
+ * Outputs: out_A, out_accepted [n_steps·C] and out_E [n_steps·C][2] = (E_current, E_new) at index s·C + c.  Where
+ * want_eval[s] is set, the e-th such step writes out_eval_loss[e][c] = the mean CE of the kept state under forward
+ * 6n + 3 and out_eval_sumsq[e][c][v] = Σθ² of canonical variable v of the kept state — the pieces of
+ * negative_log_posterior, as hmcx_mlp_sgd_run returns them.  Where want_draw[s] is set, the d-th such step of
+ * chain c stores the kept state at draws.p[v] + (c·draw_stride + d)·n_v and, where out_mom.p[v] is given, the
+ * momentum drawn in that step at the same offset of out_mom.p[v].
+ * Guarantees:
+ *   chains   with PHILOX noise and masks chain c is bit for bit the C = 1 call with chain0 + c — state, A, E,
+ *            flags, evaluations, draws, float64 and float32: a chain's result depends neither on C, nor on how the
+ *            chains are grouped into launches, nor on the other chains' path lengths.
+ *   splits   one call of n steps equals any split into calls that carry par and advance step_base (and the
+ *            host arrays and the draw pointers), bit for bit.
+ *   errors   invalid arguments return a negative code, set hmcx_last_error, launch nothing and leave par
+ *            untouched: C outside 1 .. 64, order not a permutation, n_iter < 0 or so large that
+ *            0x80000000 + 6n + 3 wraps, chain0 + C or step_base + n_steps wrapping 2^32, want_draw with
+ *            draw_stride below the call's flagged steps, a missing buffer for the chosen modes; NULL ctx or
+ *            args: −1.
+ *   n_steps == 0 does nothing.
+ * Schedule: the chains are the problems of batched launches, in groups of at most 6; gradient evaluation e of a
+ * step is launched for the chains of the group that still have one, so a step costs max_c(1 + 6·n_c) evaluations.
+ * Only unfused launches: no cross-workgroup exchange, no spin-wait, no abort word.  Nothing is read back inside
+ * the call.  Stream-ordered; returns once enqueued. */
+typedef struct hmcx_mlp_hmc_chains_args {
+  int dtype;
+  int B, n_in, n_mid, n_out, n_steps;
+  int C;                      /* chains, 1 .. 64 */
+  int order[6];               /* canonical variable indices 0=W1 .. 5=b3 in the caller's start order */
+  double alpha;
+  const void* X;              /* device [B][n_in] */
+  const int32_t* y;           /* device [B] labels */
+  const double* eps;          /* host [n_steps] */
+  const int32_t* n_iter;      /* host [n_steps*C] */
+  const double* u_accept;     /* host [n_steps*C] */
+  int noise_mode;             /* HMCX_NOISE_BUFFER or HMCX_NOISE_PHILOX */
+  const double* noise;        /* device, BUFFER */
+  const int64_t* noise_off;   /* host [n_steps*C], BUFFER */
+  int mask_mode;              /* HMCX_MLP_MASKS_NONE / _FIXED / _PHILOX */
+  const void* masks;          /* device (dtype), FIXED */
+  const int64_t* mask_off;    /* host [n_steps*C], FIXED: forward f of (s, c) at + f·3·B·n_mid */
+  uint64_t seed;
+  uint32_t chain0, step_base; /* chain c draws under Philox chain chain0 + c */
+  hmcx_mlp_params par;        /* [C][shape_v] per variable, updated in place */
+  double* out_A;              /* device [n_steps*C] */
+  int32_t* out_accepted;      /* device [n_steps*C] */
+  double* out_E;              /* device [n_steps*C][2] or NULL */
+  const uint8_t* want_eval;   /* host [n_steps] or NULL */
+  double* out_eval_loss;      /* device [n_evals][C] */
+  double* out_eval_sumsq;     /* device [n_evals][C][6] or NULL */
+  const uint8_t* want_draw;   /* host [n_steps] or NULL */
+  hmcx_mlp_params draws;      /* device, [C][draw_stride][shape_v] per variable (read where want_draw is given) */
+  int64_t draw_stride;        /* draws per chain of the caller's buffers */
+  hmcx_mlp_params out_mom;    /* device, the layout of draws; all NULL: the momentum is not stored */
+} hmcx_mlp_hmc_chains_args;
+int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a);
+
 /* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
  * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
  * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
