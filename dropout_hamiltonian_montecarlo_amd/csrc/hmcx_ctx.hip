@@ -1,7 +1,9 @@
 // hmcx_ctx.hip — context, workspace, staging, hipGraph capture, the C ABI (include/hmcx.h),
-// and the full-batch HMC kernel for the MVN model (config 1).
+// and the full-batch HMC kernel for the MVN model (config 1).  The MLP entry points at the end of the file check
+// their arguments through hmcx_mlp_checks.h (plain host C++, testable without a device) and dispatch on dtype.
 #include "hmcx_common.h"
 #include "hmcx_internal.h"
+#include "hmcx_mlp_checks.h"
 #include <new>
 #include <cstdio>
 #include <cstring>
@@ -1055,28 +1057,15 @@ int hmcx_mh_mvn_run(hmcx_ctx* ctx, const hmcx_mh_mvn_args* a) {
   return mh_mvn_run(ctx, a);
 }
 
-static int check_mlp(hmcx_ctx* ctx, int dtype, int B, int n_in, int n_mid, int n_out) {
-  if (dtype != HMCX_F32 && dtype != HMCX_F64) return set_error(ctx, HMCX_EINVAL, "dtype must be HMCX_F32/HMCX_F64");
-  if (B < 1 || n_in < 1 || n_mid < 1 || n_out < 1) return set_error(ctx, HMCX_EINVAL, "mlp: sizes must be >= 1");
-  if ((long long)B * n_mid * 3 > 0x7fffffffLL || (long long)n_mid * n_in > 0x7fffffffLL ||
-      (long long)n_mid * n_mid > 0x7fffffffLL)
-    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp: layer too large");
-  return HMCX_OK;
-}
-
-static bool mlp_par_ok(const hmcx_mlp_params* p) {
-  if (!p) return false;
-  for (int v = 0; v < 6; ++v)
-    if (!p->p[v]) return false;
-  return true;
+// The MLP entry points: guard, hmcx_mlp_checks.h (a failed check is the context's error), dispatch on dtype.
+static int checked(hmcx_ctx* ctx, const mlp_checks::MlpCheck& r) {
+  return r.status == HMCX_OK ? HMCX_OK : set_error(ctx, r.status, r.msg);
 }
 
 int hmcx_mlp_masks(hmcx_ctx* ctx, int dtype, int B, int n_mid, uint64_t seed, uint32_t chain, uint32_t step,
                    uint32_t slot, void* out) {
   HMCX_GUARD_CTX(ctx);
-  int rc = check_mlp(ctx, dtype, B, 1, n_mid, 1);
-  if (rc) return rc;
-  if (!out) return set_error(ctx, HMCX_EINVAL, "null pointer");
+  if (int rc = checked(ctx, mlp_checks::masks(dtype, B, n_mid, out))) return rc;
   return dtype == HMCX_F64 ? mlp_masks_t<double>(ctx, B, n_mid, seed, chain, step, slot, out)
                            : mlp_masks_t<float>(ctx, B, n_mid, seed, chain, step, slot, out);
 }
@@ -1085,9 +1074,7 @@ int hmcx_mlp_grad(hmcx_ctx* ctx, int dtype, const void* X, const int32_t* y, int
                   const hmcx_mlp_params* par, const void* masks, double alpha, hmcx_mlp_params* grads,
                   double* loss) {
   HMCX_GUARD_CTX(ctx);
-  int rc = check_mlp(ctx, dtype, B, n_in, n_mid, n_out);
-  if (rc) return rc;
-  if (!X || !y || !mlp_par_ok(par) || !mlp_par_ok(grads)) return set_error(ctx, HMCX_EINVAL, "null pointer");
+  if (int rc = checked(ctx, mlp_checks::grad(dtype, X, y, B, n_in, n_mid, n_out, par, grads))) return rc;
   return dtype == HMCX_F64 ? mlp_grad_t<double>(ctx, X, y, B, n_in, n_mid, n_out, par, masks, alpha, grads, loss)
                            : mlp_grad_t<float>(ctx, X, y, B, n_in, n_mid, n_out, par, masks, alpha, grads, loss);
 }
@@ -1095,256 +1082,33 @@ int hmcx_mlp_grad(hmcx_ctx* ctx, int dtype, const void* X, const int32_t* y, int
 int hmcx_mlp_loss(hmcx_ctx* ctx, int dtype, const void* X, const int32_t* y, int B, int n_in, int n_mid, int n_out,
                   const hmcx_mlp_params* par, const void* masks, double* loss, void* logits) {
   HMCX_GUARD_CTX(ctx);
-  int rc = check_mlp(ctx, dtype, B, n_in, n_mid, n_out);
-  if (rc) return rc;
-  if (!X || !mlp_par_ok(par)) return set_error(ctx, HMCX_EINVAL, "null pointer");
-  if (!y && !logits) return set_error(ctx, HMCX_EINVAL, "mlp_loss: need labels or a logits output");
+  if (int rc = checked(ctx, mlp_checks::loss(dtype, X, y, B, n_in, n_mid, n_out, par, logits))) return rc;
   return dtype == HMCX_F64 ? mlp_loss_t<double>(ctx, X, y, B, n_in, n_mid, n_out, par, masks, loss, logits)
                            : mlp_loss_t<float>(ctx, X, y, B, n_in, n_mid, n_out, par, masks, loss, logits);
 }
 
-int hmcx_mlp_sghmc_run(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "n_steps < 0");
-  if (!a->X || !a->y || !a->row0 || !a->eps || !a->n_iter || !a->u_accept || !mlp_par_ok(&a->par) || !a->out_A ||
-      !a->out_accepted || !a->out_loss)
-    return set_error(ctx, HMCX_EINVAL, "mlp sghmc: null pointer");
-  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "bad noise_mode");
-  if (a->mask_mode != HMCX_NOISE_BUFFER && a->mask_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "bad mask_mode");
-  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
-    return set_error(ctx, HMCX_EINVAL, "BUFFER noise mode needs noise and noise_off");
-  if (a->mask_mode == HMCX_NOISE_BUFFER && (!a->masks || !a->mask_off))
-    return set_error(ctx, HMCX_EINVAL, "BUFFER mask mode needs masks and mask_off");
-  if (a->n_steps == 0) return HMCX_OK;
-  return a->dtype == HMCX_F64 ? mlp_sghmc_t<double>(ctx, a) : mlp_sghmc_t<float>(ctx, a);
-}
-
 int hmcx_mlp_hmc_leapfrog(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* a) {
   HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_iter < 0) return set_error(ctx, HMCX_EINVAL, "mlp leapfrog: n_iter < 0");
-  if (!a->X || !a->y || !mlp_par_ok(&a->q) || !mlp_par_ok(&a->p) || !mlp_par_ok(&a->g))
-    return set_error(ctx, HMCX_EINVAL, "mlp leapfrog: null pointer");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp leapfrog: bad mask_mode");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && !a->masks)
-    return set_error(ctx, HMCX_EINVAL, "mlp leapfrog: masks required for FIXED / PHILOX");
-  int seen = 0;
-  for (int i = 0; i < 6; ++i) {
-    const int v = a->order[i];
-    if (v < 0 || v > 5 || ((seen >> v) & 1))
-      return set_error(ctx, HMCX_EINVAL, "mlp leapfrog: order must be a permutation of 0..5");
-    seen |= 1 << v;
-  }
+  if (int rc = checked(ctx, mlp_checks::leapfrog(a))) return rc;
   return a->dtype == HMCX_F64 ? mlp_leapfrog_t<double>(ctx, a) : mlp_leapfrog_t<float>(ctx, a);
 }
 
-int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgd: n_steps < 0");
-  if (!a->X || !a->y || !a->row0 || !mlp_par_ok(&a->par) || !mlp_par_ok(&a->mom))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgd: null pointer");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgd: bad mask_mode");
-  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgd: FIXED masks need masks and mask_off");
-  if (a->want_eval && !a->out_eval_loss) return set_error(ctx, HMCX_EINVAL, "mlp sgd: want_eval needs out_eval_loss");
-  if (a->want_eval && a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->eval_mask_off)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgd: FIXED masks with want_eval need eval_mask_off");
-  for (int s = 0; s < a->n_steps; ++s)
-    if (a->row0[s] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgd: negative row0");
-  if (a->n_steps == 0) return HMCX_OK;
-  return a->dtype == HMCX_F64 ? mlp_sgd_t<double>(ctx, a) : mlp_sgd_t<float>(ctx, a);
-}
-
-int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld: n_steps < 0");
-  // the noise index of an element is a 32-bit Philox counter field: all six variables together stay below 2^31
-  if ((long long)a->n_mid * a->n_in + (long long)a->n_mid * a->n_mid + (long long)a->n_out * a->n_mid +
-          2LL * a->n_mid + a->n_out > 0x7fffffffLL)
-    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp sgld: more than 2^31 - 1 parameters");
-  if (a->variant != 0 && a->variant != 1) return set_error(ctx, HMCX_EINVAL, "mlp sgld: variant must be 0 or 1");
-  if (!a->X || !a->y || !a->row0 || !a->eps || !mlp_par_ok(&a->par) || (a->variant == 1 && !mlp_par_ok(&a->mom)))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: null pointer");
-  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: bad noise_mode");
-  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: BUFFER noise mode needs noise and noise_off");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: bad mask_mode");
-  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: FIXED masks need masks and mask_off");
-  if (a->want_eval && !a->out_eval_loss) return set_error(ctx, HMCX_EINVAL, "mlp sgld: want_eval needs out_eval_loss");
-  if (a->want_eval && a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->eval_mask_off)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld: FIXED masks with want_eval need eval_mask_off");
-  if (a->want_draw && !mlp_par_ok(&a->draws)) return set_error(ctx, HMCX_EINVAL, "mlp sgld: want_draw needs draws");
-  int seen = 0;
-  for (int i = 0; i < 6; ++i) {
-    const int v = a->order[i];
-    if (v < 0 || v > 5 || ((seen >> v) & 1))
-      return set_error(ctx, HMCX_EINVAL, "mlp sgld: order must be a permutation of 0..5");
-    seen |= 1 << v;
-  }
-  for (int s = 0; s < a->n_steps; ++s) {
-    if (a->row0[s] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld: negative row0");
-    if (a->noise_mode == HMCX_NOISE_BUFFER && a->noise_off[s] < 0)
-      return set_error(ctx, HMCX_EINVAL, "mlp sgld: negative noise_off");
-    if (a->want_eval && a->want_eval[s] > 3) return set_error(ctx, HMCX_EINVAL, "mlp sgld: want_eval holds bits 0 and 1");
-  }
-  if (a->n_steps == 0) return HMCX_OK;
-  return a->dtype == HMCX_F64 ? mlp_sgld_t<double>(ctx, a) : mlp_sgld_t<float>(ctx, a);
-}
-
-int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: n_steps < 0");
-  if (a->C < 1 || a->C > 64) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: C must be 1 .. 64");
-  if ((uint64_t)a->chain0 + (uint64_t)a->C > 0x100000000ULL)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: chain0 + C wraps 2^32");
-  if ((uint64_t)a->step_base + (uint64_t)a->n_steps > 0x100000000ULL)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: step_base + n_steps wraps 2^32");
-  if ((long long)a->n_mid * a->n_in + (long long)a->n_mid * a->n_mid + (long long)a->n_out * a->n_mid +
-          2LL * a->n_mid + a->n_out > 0x7fffffffLL)
-    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp sgld chains: more than 2^31 - 1 parameters");
-  if (a->variant != 0 && a->variant != 1)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: variant must be 0 or 1");
-  if (!a->X || !a->y || !a->row0 || !a->eps || !mlp_par_ok(&a->par) || (a->variant == 1 && !mlp_par_ok(&a->mom)))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: null pointer");
-  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: bad noise_mode");
-  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: BUFFER noise mode needs noise and noise_off");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: bad mask_mode");
-  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: FIXED masks need masks and mask_off");
-  if (a->want_eval && !a->out_eval_loss)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_eval needs out_eval_loss");
-  if (a->want_eval && a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->eval_mask_off)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: FIXED masks with want_eval need eval_mask_off");
-  if (a->want_draw && !mlp_par_ok(&a->draws))
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_draw needs draws");
-  int seen = 0;
-  for (int i = 0; i < 6; ++i) {
-    const int v = a->order[i];
-    if (v < 0 || v > 5 || ((seen >> v) & 1))
-      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: order must be a permutation of 0..5");
-    seen |= 1 << v;
-  }
-  int64_t n_draws = 0;
-  for (int s = 0; s < a->n_steps; ++s) {
-    if (a->row0[s] < 0) return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: negative row0");
-    if (a->noise_mode == HMCX_NOISE_BUFFER && a->noise_off[s] < 0)
-      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: negative noise_off");
-    if (a->want_eval && a->want_eval[s] > 3)
-      return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: want_eval holds bits 0 and 1");
-    if (a->want_draw && a->want_draw[s]) ++n_draws;
-  }
-  if (n_draws > a->draw_stride)
-    return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: draw_stride below the call's flagged steps");
-  if (a->n_steps == 0) return HMCX_OK;
-  return a->dtype == HMCX_F64 ? mlp_sgld_chains_t<double>(ctx, a) : mlp_sgld_chains_t<float>(ctx, a);
-}
-
-int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a) {
-  HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->B, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->n_steps < 0) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_steps < 0");
-  if (a->C < 1 || a->C > 64) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: C must be 1 .. 64");
-  if ((uint64_t)a->chain0 + (uint64_t)a->C > 0x100000000ULL)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: chain0 + C wraps 2^32");
-  if ((uint64_t)a->step_base + (uint64_t)a->n_steps > 0x100000000ULL)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: step_base + n_steps wraps 2^32");
-  // the noise index of an element is a 32-bit Philox counter field: all six variables together stay below 2^31
-  if ((long long)a->n_mid * a->n_in + (long long)a->n_mid * a->n_mid + (long long)a->n_out * a->n_mid +
-          2LL * a->n_mid + a->n_out > 0x7fffffffLL)
-    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp hmc chains: more than 2^31 - 1 parameters");
-  if (!a->X || !a->y || !a->eps || !a->n_iter || !a->u_accept || !mlp_par_ok(&a->par) || !a->out_A || !a->out_accepted)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: null pointer");
-  if (a->noise_mode != HMCX_NOISE_BUFFER && a->noise_mode != HMCX_NOISE_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: bad noise_mode");
-  if (a->noise_mode == HMCX_NOISE_BUFFER && (!a->noise || !a->noise_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: BUFFER noise mode needs noise and noise_off");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: bad mask_mode");
-  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && (!a->masks || !a->mask_off))
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: FIXED masks need masks and mask_off");
-  if (a->want_eval && !a->out_eval_loss)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: want_eval needs out_eval_loss");
-  if (a->want_draw && !mlp_par_ok(&a->draws))
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: want_draw needs draws");
-  int seen = 0;
-  for (int i = 0; i < 6; ++i) {
-    const int v = a->order[i];
-    if (v < 0 || v > 5 || ((seen >> v) & 1))
-      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: order must be a permutation of 0..5");
-    seen |= 1 << v;
-  }
-  int64_t n_draws = 0;
-  for (int64_t j = 0; j < (int64_t)a->n_steps * a->C; ++j) {
-    if (a->n_iter[j] < 0) return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_iter < 0");
-    // the mask slot of the step's last forward, 0x80000000 + 6n + 3, stays below 2^32
-    if ((int64_t)a->n_iter[j] > (0x7fffffffLL - 3) / 6)
-      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: n_iter so large that the forward number wraps 2^32");
-    if (a->noise_mode == HMCX_NOISE_BUFFER && a->noise_off[j] < 0)
-      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: negative noise_off");
-    if (a->mask_mode == HMCX_MLP_MASKS_FIXED && a->mask_off[j] < 0)
-      return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: negative mask_off");
-  }
-  for (int s = 0; s < a->n_steps; ++s)
-    if (a->want_draw && a->want_draw[s]) ++n_draws;
-  if (n_draws > a->draw_stride)
-    return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: draw_stride below the call's flagged steps");
-  if (a->n_steps == 0) return HMCX_OK;
-  return a->dtype == HMCX_F64 ? mlp_hmc_chains_t<double>(ctx, a) : mlp_hmc_chains_t<float>(ctx, a);
-}
+// The stepping calls: a failed check or n_steps == 0 launches nothing.
+#define HMCX_MLP_RUN(check, run)                              \
+  HMCX_GUARD_CTX(ctx);                                        \
+  if (int rc = checked(ctx, mlp_checks::check(a))) return rc; \
+  if (a->n_steps == 0) return HMCX_OK;                        \
+  return a->dtype == HMCX_F64 ? run<double>(ctx, a) : run<float>(ctx, a)
+int hmcx_mlp_sghmc_run(hmcx_ctx* ctx, const hmcx_mlp_sghmc_args* a) { HMCX_MLP_RUN(sghmc, mlp_sghmc_t); }
+int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a) { HMCX_MLP_RUN(sgd, mlp_sgd_t); }
+int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a) { HMCX_MLP_RUN(sgld, mlp_sgld_t); }
+int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a) { HMCX_MLP_RUN(sgld_chains, mlp_sgld_chains_t); }
+int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a) { HMCX_MLP_RUN(hmc_chains, mlp_hmc_chains_t); }
+#undef HMCX_MLP_RUN
 
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   HMCX_GUARD_CTX(ctx);
-  if (!a) return set_error(ctx, HMCX_EINVAL, "null args");
-  int rc = check_mlp(ctx, a->dtype, a->N, a->n_in, a->n_mid, a->n_out);
-  if (rc) return rc;
-  if (a->S < 1 || a->T < 1) return set_error(ctx, HMCX_EINVAL, "mlp predictive: S and T must be >= 1");
-  const long long D = (long long)a->S * a->T;
-  if (D > 0x7fffffffLL || D * a->N > 0x7fffffffLL * 64)
-    return set_error(ctx, HMCX_EUNSUPPORTED, "mlp predictive: too many draws");
-  if (!a->X || !mlp_par_ok(&a->par)) return set_error(ctx, HMCX_EINVAL, "mlp predictive: null pointer");
-  if (a->mask_mode != HMCX_MLP_MASKS_NONE && a->mask_mode != HMCX_MLP_MASKS_FIXED &&
-      a->mask_mode != HMCX_MLP_MASKS_PHILOX)
-    return set_error(ctx, HMCX_EINVAL, "mlp predictive: bad mask_mode");
-  if (a->mask_mode == HMCX_MLP_MASKS_NONE && a->T != 1)
-    return set_error(ctx, HMCX_EINVAL, "mlp predictive: without dropout every draw of a set is the same (T must be 1)");
-  if (a->mask_mode == HMCX_MLP_MASKS_FIXED && !a->masks)
-    return set_error(ctx, HMCX_EINVAL, "mlp predictive: FIXED masks required");
-  if (a->mask_mode == HMCX_MLP_MASKS_PHILOX && (unsigned long long)a->slot0 + (unsigned long long)D > 0x100000000ULL)
-    return set_error(ctx, HMCX_EINVAL, "mlp predictive: slot0 + S*T wraps 2^32");
-  if (!a->y && (a->out_lppd || a->out_draw_nll || a->out_draw_correct))
-    return set_error(ctx, HMCX_EINVAL, "mlp predictive: lppd / draw_nll / draw_correct need labels");
-  if (a->path < 0 || a->path > 2) return set_error(ctx, HMCX_EINVAL, "mlp predictive: path must be 0, 1 or 2");
+  if (int rc = checked(ctx, mlp_checks::predictive(a))) return rc;
   if (a->path == 2 && !mlp_pred_fused_ok(ctx, a))
     return set_error(ctx, HMCX_EUNSUPPORTED, "mlp predictive: shape not eligible for the fused path");
   return a->dtype == HMCX_F64 ? mlp_predictive_t<double>(ctx, a) : mlp_predictive_t<float>(ctx, a);

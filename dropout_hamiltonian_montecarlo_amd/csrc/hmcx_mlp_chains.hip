@@ -2,7 +2,9 @@
 // shared minibatches run the one-chain schedule (mlp_sgld_t, hmcx_mlp.hip) with every launch widened over a group
 // of up to MAXPROB chains — k_mmc (k_mmb with a problem table that also carries the buffers a chain owns),
 // k_pending_chains, k_mlp_sgld_chains.  The group forward / gradient launches are helpers (mlp_chains_forward,
-// mlp_chains_backward) that the multi-chain HMC of hmcx_mlp_hmc_chains.hip calls as well.
+// mlp_chains_backward) that the multi-chain HMC of hmcx_mlp_hmc_chains.hip calls as well; the group's nets, mask
+// sizes, workspaces and mask sources are ChainGroup's (hmcx_mlp_shared.h), the arguments are checked in
+// hmcx_mlp_checks.h before this unit is reached.
 // A unit of its own, once per dtype, so that hmcx_mlp.hip's code objects keep the layout they were measured with
 // (DESIGN.md §5.3).  The launches shared with the one-chain paths (layer 1, the n_out > 32 forward, the mask draws)
 // go through helpers of hmcx_mlp.hip seen here as prototypes only (hmcx_mlp_shared.h, hmcx_internal.h): including
@@ -289,41 +291,31 @@ __attribute__((used)) int mlp_chains_backward(hmcx_ctx* ctx, ChainList<T>& L, un
 // gradient partials (its net), loss partials, gradient buffers, Σθ² partials and mask scratches.
 template <typename T>
 int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
-  const int B = s->B, n_mid = s->n_mid, C = s->C, G = std::min(C, MAXPROB);
+  const int B = s->B, n_mid = s->n_mid, C = s->C;
   const bool philox = s->mask_mode == HMCX_MLP_MASKS_PHILOX, fixed = s->mask_mode == HMCX_MLP_MASKS_FIXED;
-  const int n3 = 3 * B * n_mid;
-  const size_t mstride = ((size_t)n3 + 63) / 64 * 64;          // a chain's mask scratch: 16-byte aligned like the first
-  MlpNet<T> cn[MAXPROB];
-  for (int c = 0; c < G; ++c) net_init(cn[c], B, s->n_in, n_mid, s->n_out, ctx->stream);
+  ChainGroup<T> grp(C, B, s->n_in, n_mid, s->n_out, ctx->stream);
+  MlpNet<T>* const cn = grp.cn;
   MlpNet<T>& net = cn[0];                                      // the group's shared dimensions, minibatch and stream
-  const int nlb = net.nlb;
+  const int G = grp.G, n3 = grp.n3, nlb = net.nlb;
+  const size_t mstride = grp.mstride;
   Workspace ws(ctx);
   T *g[6], *mscr = nullptr, *escr = nullptr;
   double *lpart, *part;
   do {
     ws.reset();
-    for (int c = 0; c < G; ++c) mlp_workspace<T>(ws, cn[c]);
+    grp.take(ws);
     lpart = ws.take<double>((size_t)G * nlb);
     for (int v = 0; v < 6; ++v) g[v] = ws.take<T>((size_t)G * net.nvar(v));
     part = ws.take<double>((size_t)G * 6 * NPART);
     if (philox) { mscr = ws.take<T>(G * mstride); escr = ws.take<T>(G * mstride); }
   } while (ws.retry());
   if (ws.failed) return HMCX_ENOMEM;
-  // k_pending_chains reaches chain c's gradient partials at c·pstride behind the first chain's: the chains'
-  // workspaces are equal chunks taken one after the other
-  auto part_of = [](const MlpNet<T>& n, int v) -> const T* {
-    return v == 1 ? n.pb1 : v == 3 ? n.pb2 : v == 4 ? n.pw3 : n.pb3;
-  };
-  const int64_t pstride = G > 1 ? (int64_t)(cn[1].pb1 - cn[0].pb1) : 0;
-  for (int c = 0; c < G; ++c)
-    for (int v : {1, 3, 4, 5})
-      if (part_of(cn[c], v) != part_of(cn[0], v) + (int64_t)c * pstride)
-        return set_error(ctx, HMCX_EINVAL, "mlp sgld chains: the chains' workspaces are not equally spaced");
+  if (int rc = grp.spacing(ctx, "mlp sgld chains: ")) return rc;
+  const int64_t pstride = grp.pstride;
   if (int rc = timing_begin(ctx, ctx->stream)) return rc;
   const T* const X0 = (const T*)s->X;
   const int nm = n_mid, n_out = s->n_out;
-  const int ng = (n3 + 63) / 64;                               // mask groups: one thread each
-  const unsigned xrows = (unsigned)(((size_t)(ng + 255) / 256 + 1 + NPART - 1) / NPART);
+  const unsigned xrows = grp.mask_rows(1, 1);                  // behind the loss block
   int nmax_pend = 0;
   for (int v : {1, 3, 4, 5}) nmax_pend = std::max(nmax_pend, net.nvar(v));
   for (int c0 = 0; c0 < C; c0 += MAXPROB) {
@@ -345,10 +337,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
       k.vt.p[v] = s->variant == 1 ? (void*)((T*)s->mom.p[v] + (size_t)c0 * (size_t)net.nvar(v)) : nullptr;
       k.vt.qn[v] = g[v]; k.vt.n[v] = net.nvar(v);
     }
-    for (int i = 0, off = 0; i < 6; ++i) {                     // the noise layout: variable after variable in `order`
-      k.vt.e0[s->order[i]] = off;
-      off += net.nvar(s->order[i]);
-    }
+    grp.noise_layout(s->order, k.vt.e0);
     k.variant = s->variant; k.noise_mode = s->noise_mode;
     k.seed = s->seed; k.chain = s->chain0 + (uint32_t)c0;
     k.part = part; k.lpart = lpart; k.nlb = nlb; k.B = B;
@@ -358,11 +347,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
     // `scr`, NONE nothing
     MaskSrc<T>* const ms = L.ms;
     auto masks_of = [&](int64_t off, const T* scr) {
-      for (int c = 0; c < np; ++c) {
-        const T* m = fixed ? (const T*)s->masks + off : philox ? scr + c * mstride : nullptr;
-        ms[c] = MaskSrc<T>{m, nullptr, T(1), B * n_mid};
-        cn[c].vec_masks = n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
-      }
+      for (int c = 0; c < np; ++c) ms[c] = grp.mask_src(c, s->mask_mode, fixed ? (const T*)s->masks + off : nullptr, scr);
     };
     // the group's forward at its chains' θ (want: with the layer-3 backward pieces of the gradient)
     auto forward = [&](bool want) -> int { return mlp_chains_forward<T>(ctx, L, want ? 63u : 0u, true); };
@@ -386,7 +371,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
         int j = 0;
         for (int v : {1, 3, 4, 5}) {
           pc.n[j] = net.nvar(v);
-          pc.part[j] = part_of(cn[0], v);
+          pc.part[j] = grp.part_of(cn[0], v);
           pc.W[j] = q[0][v];
           pc.G[j] = g[v];
           ++j;

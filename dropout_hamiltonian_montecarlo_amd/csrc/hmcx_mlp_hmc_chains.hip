@@ -4,7 +4,9 @@
 // A unit of its own, once per dtype.  The GEMM launches go through helpers seen here as prototypes only
 // (hmcx_mlp_shared.h: mlp_chains_forward / mlp_chains_backward of hmcx_mlp_chains.hip, which reach mlp_layer1_batch
 // and mlp_forward of hmcx_mlp.hip), so this unit's code object holds its own element-wise kernels and nothing else:
-// k_hmc_start, k_hmc_kicks, k_hmc_ends, k_hmc_accept, k_hmc_commit, k_hmc_eval.
+// k_hmc_start, k_hmc_kicks, k_hmc_ends, k_hmc_accept, k_hmc_commit, k_hmc_eval.  The launch group's nets, mask sizes,
+// workspaces, noise layout and mask sources are ChainGroup's (hmcx_mlp_shared.h); the arguments are checked in
+// hmcx_mlp_checks.h before this unit is reached.
 #include "hmcx_mlp_kernels.h"
 #include "hmcx_mlp_shared.h"
 #include <algorithm>
@@ -298,24 +300,21 @@ __global__ void k_hmc_eval(const double* lpart, int64_t lstride, int nlb, int B,
 // not the chain goes on: what is launched for a chain depends on (e, n_c) alone, never on the other chains.
 template <typename T>
 int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
-  const int B = s->B, n_mid = s->n_mid, C = s->C, G = std::min(C, MAXPROB);
-  const bool philox = s->mask_mode == HMCX_MLP_MASKS_PHILOX, fixed = s->mask_mode == HMCX_MLP_MASKS_FIXED;
-  const int n3 = 3 * B * n_mid;
-  const size_t mstride = ((size_t)n3 + 63) / 64 * 64;          // a chain's mask scratch: 16-byte aligned like the first
-  MlpNet<T> cn[MAXPROB];
-  for (int c = 0; c < G; ++c) {
-    net_init(cn[c], B, s->n_in, n_mid, s->n_out, ctx->stream);
-    cn[c].X = (const T*)s->X; cn[c].y = s->y;
-  }
+  const int B = s->B, n_mid = s->n_mid, C = s->C;
+  const bool philox = s->mask_mode == HMCX_MLP_MASKS_PHILOX;
+  ChainGroup<T> grp(C, B, s->n_in, n_mid, s->n_out, ctx->stream);
+  MlpNet<T>* const cn = grp.cn;
   MlpNet<T>& net = cn[0];
-  const int nlb = net.nlb;
+  const int G = grp.G, n3 = grp.n3, ng = grp.ng, nlb = net.nlb;
+  const size_t mstride = grp.mstride;
+  for (int c = 0; c < G; ++c) { cn[c].X = (const T*)s->X; cn[c].y = s->y; }
   Workspace ws(ctx);
   T *g[6], *qn[6], *p[6], *mA = nullptr, *mB = nullptr;
   double *lpA, *lpB, *part;
   int32_t* acc;
   do {
     ws.reset();
-    for (int c = 0; c < G; ++c) mlp_workspace<T>(ws, cn[c]);
+    grp.take(ws);
     lpA = ws.take<double>((size_t)G * nlb);
     lpB = ws.take<double>((size_t)G * nlb);
     for (int v = 0; v < 6; ++v) {
@@ -328,21 +327,11 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
     if (philox) { mA = ws.take<T>(G * mstride); mB = ws.take<T>(G * mstride); }
   } while (ws.retry());
   if (ws.failed) return set_error(ctx, HMCX_ENOMEM, "mlp hmc chains: the workspace of one launch group does not fit in device memory");
-  // the kicks reach chain ci's gradient partials at ci·pstride behind the first chain's: the chains' workspaces
-  // are equal chunks taken one after the other
-  auto part_of = [](const MlpNet<T>& n, int v) -> const T* {
-    return v == 1 ? n.pb1 : v == 3 ? n.pb2 : v == 4 ? n.pw3 : v == 5 ? n.pb3 : nullptr;
-  };
-  const int64_t pstride = G > 1 ? (int64_t)(cn[1].pb1 - cn[0].pb1) : 0;
-  for (int c = 0; c < G; ++c)
-    for (int v : {1, 3, 4, 5})
-      if (part_of(cn[c], v) != part_of(cn[0], v) + (int64_t)c * pstride)
-        return set_error(ctx, HMCX_EINVAL, "mlp hmc chains: the chains' workspaces are not equally spaced");
+  if (int rc = grp.spacing(ctx, "mlp hmc chains: ")) return rc;
+  const int64_t pstride = grp.pstride;
   if (int rc = timing_begin(ctx, ctx->stream)) return rc;
   const int* o = s->order;
-  const int ng = (n3 + 63) / 64;                               // mask groups of one forward: one thread each
-  const unsigned mrows1 = (unsigned)(((size_t)(ng + 255) / 256 + NPART - 1) / NPART);
-  const unsigned mrows2 = (unsigned)(((size_t)(2 * (size_t)ng + 255) / 256 + NPART - 1) / NPART);
+  const unsigned mrows1 = grp.mask_rows(1), mrows2 = grp.mask_rows(2);
   for (int c0 = 0; c0 < C; c0 += MAXPROB) {
     const int np = std::min(MAXPROB, C - c0);
     T *qc[MAXPROB][6], *qnc[MAXPROB][6], *gc[MAXPROB][6];
@@ -356,10 +345,7 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
         gc[c][v] = g[v] + (size_t)c * net.nvar(v);
       }
     }
-    for (int i = 0, off = 0; i < 6; ++i) {                     // the noise layout: variable after variable in `order`
-      gr.e0[o[i]] = off;
-      off += net.nvar(o[i]);
-    }
+    grp.noise_layout(o, gr.e0);
     gr.part = part; gr.mA = mA; gr.mB = mB; gr.mstride = (int64_t)mstride; gr.n3 = n3;
     gr.seed = s->seed; gr.chain = s->chain0 + (uint32_t)c0;
     // a forward of the listed chains (group indices) at q' or q under forward number f[ci] of the step
@@ -369,12 +355,11 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
       L.n = n;
       for (int j = 0; j < n; ++j) {
         const int ci = idx[j];
-        const T* m = fixed ? (const T*)s->masks + s->mask_off[sc + ci] + f[ci] * (int64_t)n3
-                   : philox ? scr + ci * mstride : nullptr;
+        const T* fm = s->mask_mode == HMCX_MLP_MASKS_FIXED
+                          ? (const T*)s->masks + s->mask_off[sc + ci] + f[ci] * (int64_t)n3 : nullptr;
         L.net[j] = &cn[ci]; L.q[j] = proposal ? qnc[ci] : qc[ci]; L.g[j] = gc[ci];
-        L.ms[j] = MaskSrc<T>{m, nullptr, T(1), B * n_mid};
+        L.ms[j] = grp.mask_src(ci, s->mask_mode, fm, scr);
         L.lpart[j] = lp + (size_t)ci * nlb;
-        cn[ci].vec_masks = n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
       }
     };
     int n_eval = 0, n_draw = 0;
@@ -426,8 +411,8 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
         if (vu >= 0) { k.p_u = p[vu]; k.g_u = g[vu]; k.q_u = qn[vu]; k.n_u = net.nvar(vu); }
         if (any_nv) { k.p_v = p[vn]; k.g_v = g[vn]; k.q_v = qn[vn]; k.n_v = net.nvar(vn); }
         k.eu = (T)eps; k.hv = (T)(0.5 * eps); k.ev = (T)eps; k.half_alpha = (T)(0.5 * s->alpha);
-        k.part_u = vu >= 0 ? part_of(cn[0], vu) : nullptr;
-        k.part_v = any_nv ? part_of(cn[0], vn) : nullptr;
+        k.part_u = vu >= 0 ? grp.part_of(cn[0], vu) : nullptr;
+        k.part_v = any_nv ? grp.part_of(cn[0], vn) : nullptr;
         k.pstride = pstride; k.nparts = nlb;
         const bool kmasks = philox && any_nv;
         k.masks = kmasks ? mA : nullptr; k.mstride = (int64_t)mstride; k.n3 = n3;

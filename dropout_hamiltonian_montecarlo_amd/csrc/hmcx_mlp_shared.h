@@ -1,7 +1,7 @@
 // hmcx_mlp_shared.h — the rest of what the MLP's compile units share, behind hmcx_mlp_kernels.h: the SGD / SGLD
-// update kernels, the net of one forward / backward (MlpNet) and prototypes of the launch helpers that hmcx_mlp.hip
-// defines.  A unit that sees only the prototypes (hmcx_mlp_chains.hip, hmcx_mlp_hmc_chains.hip) instantiates none of
-// the kernels they launch.
+// update kernels, the net of one forward / backward (MlpNet), prototypes of the launch helpers that hmcx_mlp.hip
+// defines and the launch group of the two chain schedules (ChainGroup, host only).  A unit that sees only the
+// prototypes (hmcx_mlp_chains.hip, hmcx_mlp_hmc_chains.hip) instantiates none of the kernels they launch.
 // hmcx_mlp.hip includes it behind its own static kernels: those are emitted in definition order.
 #pragma once
 #include "hmcx_mlp_kernels.h"
@@ -239,4 +239,50 @@ template <typename T> struct ChainList {
 // (pb1, pb2, pw3, pb3) for the caller's element-wise kernel.  mlp_grad_launch's launches and flags per chain.
 template <typename T> int mlp_chains_forward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, bool layer1);
 template <typename T> int mlp_chains_backward(hmcx_ctx* ctx, ChainList<T>& L, unsigned want, double alpha);
+
+// The launch group of the two chain schedules (mlp_sgld_chains_t, mlp_hmc_chains_t), host only: the nets of up to
+// MAXPROB chains that share dimensions, minibatch and stream, and what follows from them.  The schedules keep
+// their own buffers, kernels, argument blocks and step loops.
+template <typename T> struct ChainGroup {
+  MlpNet<T> cn[MAXPROB];
+  int G;                                 // chains of a full group: min(C, MAXPROB)
+  int n3, ng;                            // mask values of one forward and their groups of 64 (one thread each)
+  size_t mstride;                        // a chain's mask scratch: 16-byte aligned like the first
+  int64_t pstride = 0;                   // elements between two chains' gradient partials (spacing())
+  ChainGroup(int C, int B, int n_in, int n_mid, int n_out, hipStream_t st)
+      : G(C < MAXPROB ? C : MAXPROB), n3(3 * B * n_mid), ng((n3 + 63) / 64), mstride(((size_t)n3 + 63) / 64 * 64) {
+    for (int c = 0; c < G; ++c) net_init(cn[c], B, n_in, n_mid, n_out, st);
+  }
+  // grid rows of NPART blocks that draw the masks of `forwards` forwards behind `extra` other blocks
+  unsigned mask_rows(int forwards, int extra = 0) const {
+    return (unsigned)(((size_t)((size_t)forwards * ng + 255) / 256 + extra + NPART - 1) / NPART);
+  }
+  void take(Workspace& ws) { for (int c = 0; c < G; ++c) mlp_workspace<T>(ws, cn[c]); }
+  // the row-block partials of a bias / W3 gradient (canonical v = 1, 3, 4, 5; null for W1 and W2)
+  static const T* part_of(const MlpNet<T>& n, int v) {
+    return v == 1 ? n.pb1 : v == 3 ? n.pb2 : v == 4 ? n.pw3 : v == 5 ? n.pb3 : nullptr;
+  }
+  // after the takes: the element-wise kernels reach chain c's partials at c·pstride behind the first chain's
+  int spacing(hmcx_ctx* ctx, const char* who) {
+    pstride = G > 1 ? (int64_t)(cn[1].pb1 - cn[0].pb1) : 0;
+    for (int c = 0; c < G; ++c)
+      for (int v : {1, 3, 4, 5})
+        if (part_of(cn[c], v) != part_of(cn[0], v) + (int64_t)c * pstride)
+          return set_error(ctx, HMCX_EINVAL, std::string(who) + "the chains' workspaces are not equally spaced");
+    return HMCX_OK;
+  }
+  // the noise layout: variable after variable in `order`
+  void noise_layout(const int* order, int* e0) const {
+    for (int i = 0, off = 0; i < 6; ++i) {
+      e0[order[i]] = off;
+      off += cn[0].nvar(order[i]);
+    }
+  }
+  // the masks of a forward of chain c: FIXED at fixed_ptr, PHILOX the chain's part of `scratch`, NONE nothing
+  MaskSrc<T> mask_src(int c, int mode, const T* fixed_ptr, const T* scratch) {
+    const T* m = mode == HMCX_MLP_MASKS_FIXED ? fixed_ptr : mode == HMCX_MLP_MASKS_PHILOX ? scratch + c * mstride : nullptr;
+    cn[c].vec_masks = cn[c].n_mid % 4 == 0 && !(m && (uintptr_t)m % 16);
+    return MaskSrc<T>{m, nullptr, T(1), cn[c].B * cn[c].n_mid};
+  }
+};
 }  // namespace hmcx

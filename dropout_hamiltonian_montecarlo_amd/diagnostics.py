@@ -101,3 +101,18 @@ def device_diagnostics(trace, means=None, M2=None, n=0, device=None):
                                              nat.ptr(out)), "hmcx_chain_diagnostics")
     o = out.cpu().numpy().reshape(3, P)
     return o[0], o[1], o[2]
+
+
+def draws_diagnostics(device_draws, too_few):
+    """{var: (split_rhat, ess)}, each of the variable's shape, of kept draws {var: [C, T, *shape] device tensor},
+    on the device one variable at a time.  Fewer than 4 draws per chain: HmcxError(too_few(T))."""
+    import torch
+    from ._native import HmcxError
+    out = {}
+    for k, t in device_draws.items():
+        if t.shape[1] < 4:
+            raise HmcxError(too_few(t.shape[1]))
+        shape = tuple(t.shape[2:])
+        _, sr, es = device_diagnostics(t.reshape(t.shape[0], t.shape[1], -1).to(torch.float64))
+        out[k] = (sr.reshape(shape), es.reshape(shape))
+    return out

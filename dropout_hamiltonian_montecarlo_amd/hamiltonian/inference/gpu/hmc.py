@@ -274,38 +274,49 @@ class hmc:
         samp = phase(st, niter, C, rngs, True) if niter > 0 else None
         if not mvn:
             self.last_state = {'weights': st[0], 'bias': st[1]}
-        traces = [[] for _ in range(C)]
-        results = []
+        shown = [i for i in range(nburn) if self.verbose is not None and (i % burn_print == 0)]
+        A, acc, nlp, L, tr, mom = samp[:6] if samp is not None else (None,) * 6
+        if mvn:
+            posterior = lambda c: {'x': tr[:, c].copy()}
+        else:
+            posterior = lambda c: {'weights': tr[:, c, :D * K].reshape((niter,) + np.shape(self.start['weights'])),
+                                   'bias': tr[:, c, D * K:].reshape((niter,) + np.shape(self.start['bias']))}
+        results, traces = self._assemble_chains(
+            C, nburn, niter, burn and (burn[0], burn[1], burn[3]), burn and burn[2][shown], samp and (A, acc, L, nlp),
+            posterior, lambda c, i: split(before[c] if i == 0 else tr[i - 1, c]), lambda c, i: split(mom[i, c]))
+        return results, traces, samp[6] if samp is not None else None
+
+    def _assemble_chains(self, C, nburn, niter, burn, burn_losses, samp, posterior, position, momentum):
+        """Per chain, in chain order, what hmc.sample prints and returns.  burn / samp: a phase's host A, accepted
+        and L [n, C], samp also the draws' losses [niter, C]; None: no step.  burn_losses [n_printed, C] are
+        printed.  posterior(c): chain c's {var: [niter, *shape]}; position(c, i): the state draw i started from;
+        momentum(c, i): its momentum (momentum None: empty lists).  Returns the chains' (posterior, loss,
+        positions, momentums) and their per-step trace records (L as drawn)."""
+        def records(A, acc, L, n, c):
+            return ({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]), 'eps': self.step_size}
+                    for i in range(n))
+        traces, results = [[] for _ in range(C)], []
         for c in range(C):
             p_accept = None
             if burn is not None:
-                A, acc, nlp, L = burn[:4]
-                for i in range(nburn):
-                    if self.verbose is not None and (i % burn_print == 0):
-                        print('loss: {0:.4f}'.format(nlp[i, c]), file=self.out)
-                p_accept = A[-1, c]
-                traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
-                                  'eps': self.step_size} for i in range(nburn))
+                for lo in burn_losses[:, c]:
+                    print('loss: {0:.4f}'.format(lo), file=self.out)
+                p_accept = burn[0][-1, c]
+                traces[c].extend(records(*burn, nburn, c))
             _, avg_step_size = DualAveragingStepSize(self.step_size).update(p_accept)
             print('adapted step size : ', avg_step_size, file=self.out)
             if samp is None:
                 results.append(({v: np.zeros((0,) + np.shape(self.start[v])) for v in self.start}, np.zeros(0), [], []))
                 continue
-            A, acc, nlp, L, tr, mom = samp[:6]
-            traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
-                              'eps': self.step_size} for i in range(niter))
-            positions = [[split(before[c] if i == 0 else tr[i - 1, c])] for i in range(niter)]
-            momentums = [[split(mom[i, c])] for i in range(niter)]
+            A, acc, L, loss = samp
+            traces[c].extend(records(A, acc, L, niter, c))
+            positions = [[position(c, i)] for i in range(niter)]
+            momentums = [] if momentum is None else [[momentum(c, i)] for i in range(niter)]
             for i in range(niter):
                 if self.verbose and (i % (niter / 10) == 0):
-                    print('loss: {0:.4f}'.format(nlp[i, c]), file=self.out)
-            if mvn:
-                posterior = {'x': tr[:, c].copy()}
-            else:
-                posterior = {'weights': tr[:, c, :D * K].reshape((niter,) + np.shape(self.start['weights'])),
-                             'bias': tr[:, c, D * K:].reshape((niter,) + np.shape(self.start['bias']))}
-            results.append((posterior, nlp[:, c].copy(), positions, momentums))
-        return results, traces, samp[6] if samp is not None else None
+                    print('loss: {0:.4f}'.format(loss[i, c]), file=self.out)
+            results.append((posterior(c), loss[:, c].copy(), positions, momentums))
+        return results, traces
 
     # ------------------------------------------------------------------ generic path (device grads)
     def _K(self, p):                                                         # hmc.py:74-79

@@ -52,7 +52,8 @@ from dropout_hamiltonian_montecarlo_amd import _native as nat
 from dropout_hamiltonian_montecarlo_amd import diagnostics
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError
 
-from .hmc import DualAveragingStepSize, hmc
+from . import _mlp_call
+from .hmc import hmc
 from .multicore import cpu_count
 
 
@@ -95,14 +96,8 @@ class hmc_multicore(hmc):
         route: the tuple ``(split_rhat, ess)`` over the flat parameter vector, from the sampling phase's [C, T, P]
         trace."""
         if self.device_draws is not None:                                    # the MLP route: per variable
-            out = {}
-            for k, t in self.device_draws.items():
-                if t.shape[1] < 4:
-                    raise HmcxError("chain_diagnostics: need at least 4 draws per chain")
-                shape = tuple(t.shape[2:])
-                _, sr, es = diagnostics.device_diagnostics(t.reshape(t.shape[0], t.shape[1], -1).to(torch.float64))
-                out[k] = (sr.reshape(shape), es.reshape(shape))
-            return out
+            return diagnostics.draws_diagnostics(self.device_draws,
+                                                 lambda T: "chain_diagnostics: need at least 4 draws per chain")
         tr = self._diag_trace
         if tr is None:
             raise HmcxError("chain_diagnostics: no sample_multicore trace")
@@ -141,8 +136,7 @@ class hmc_multicore(hmc):
         out_acc = torch.empty(nsc, dtype=torch.int32, device=dev)
         a = nat.MlpHmcChainsArgs()
         a.dtype, a.B, a.n_in, a.n_mid, a.n_out, a.n_steps, a.C = m.code, X.shape[0], m.n_in, m.n_mid, m.n_out, n_steps, C
-        for i, v in enumerate(order):
-            a.order[i] = v
+        a.order[:] = order
         a.alpha = m.alpha
         a.X, a.y = X.data_ptr(), y.data_ptr()
         a.eps = eps.ctypes.data_as(nat.c_dblp)
@@ -150,8 +144,7 @@ class hmc_multicore(hmc):
         a.u_accept = u.ctypes.data_as(nat.c_dblp)
         a.noise_mode, a.mask_mode = nat.NOISE_PHILOX, mask_mode
         a.seed, a.chain0, a.step_base = self.seed, self.chain & 0xFFFFFFFF, self.global_step & 0xFFFFFFFF
-        for i, t in enumerate(par):
-            a.par.p[i] = t.data_ptr()
+        _mlp_call.fill_params(a.par, par)
         o_ev = 3 * nsc
         a.out_A, a.out_E, a.out_accepted = nat.ptr(out_f[:nsc]), nat.ptr(out_f[nsc:3 * nsc]), nat.ptr(out_acc)
         a.want_eval = want_eval.ctypes.data_as(nat.c_u8p)
@@ -162,12 +155,10 @@ class hmc_multicore(hmc):
             want_draw = np.ones(n_steps, dtype=np.uint8)
             draws = [torch.empty((C, n_steps) + m.shapes[k], dtype=dt, device=dev) for k in MLP_PARAM_NAMES]
             a.want_draw, a.draw_stride = want_draw.ctypes.data_as(nat.c_u8p), n_steps
-            for i, t in enumerate(draws):
-                a.draws.p[i] = t.data_ptr()
+            _mlp_call.fill_params(a.draws, draws)
             if self.keep_momentum:
                 moms = [torch.empty((C, n_steps) + m.shapes[k], dtype=dt, device=dev) for k in MLP_PARAM_NAMES]
-                for i, t in enumerate(moms):
-                    a.out_mom.p[i] = t.data_ptr()
+                _mlp_call.fill_params(a.out_mom, moms)
         ctx = nat.context(dev)
         ctx.check(ctx.lib.hmcx_mlp_hmc_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_hmc_chains_run")
         self.global_step += n_steps
@@ -195,17 +186,7 @@ class hmc_multicore(hmc):
         par = [m._dev(self.start[k]).reshape(m.shapes[k]).unsqueeze(0).repeat((C,) + (1,) * len(m.shapes[k])).contiguous()
                for k in MLP_PARAM_NAMES]
         npdt = torch.empty(0, dtype=m.dtype).numpy().dtype
-        dims = np.array([int(np.prod(m.shapes[k])) for k in MLP_PARAM_NAMES], dtype=np.float64)
-
-        def nlp(loss, sumsq):                                                # mlp.nlp_from_parts, start order
-            out = np.empty(loss.shape)
-            for e in range(loss.shape[0]):
-                for c in range(loss.shape[1]):
-                    K = 0.0
-                    for v in order:
-                        K -= 0.5 * m.alpha * float(sumsq[e, c, v]) / dims[v]
-                    out[e, c] = np.float64(loss[e, c]) + K
-            return out
+        nlp = lambda loss, sumsq: _mlp_call.nlp_from_eval(m, keys, loss, sumsq)   # noqa: E731
         burn = None
         burn_print = nburn / 10
         if nburn > 0:
@@ -224,32 +205,12 @@ class hmc_multicore(hmc):
             hmom = None if moms is None else {k: moms[k].cpu().numpy() for k in keys}
         self.last_state = {k: par[MLP_PARAM_NAMES.index(k)] for k in keys}
         self._diag_trace = None
-        traces, results = [[] for _ in range(C)], []
-        for c in range(C):
-            p_accept = None
-            if burn is not None:
-                A, acc, L, lo = burn
-                for e in range(lo.shape[0]):
-                    print('loss: {0:.4f}'.format(lo[e, c]), file=self.out)
-                p_accept = A[-1, c]
-                traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
-                                  'eps': self.step_size} for i in range(nburn))
-            _, avg_step_size = DualAveragingStepSize(self.step_size).update(p_accept)
-            print('adapted step size : ', avg_step_size, file=self.out)
-            if samp is None:
-                results.append(({v: np.zeros((0,) + np.shape(self.start[v])) for v in keys}, np.zeros(0), [], []))
-                continue
-            A, acc, L, lo = samp
-            traces[c].extend({'L': float(L[i, c]), 'A': float(A[i, c]), 'accepted': bool(acc[i, c]),
-                              'eps': self.step_size} for i in range(niter_w))
-            posterior = {k: host[k][c] for k in keys}
-            first = {k: before[MLP_PARAM_NAMES.index(k)][c] for k in keys}
-            positions = [[first if i == 0 else {k: host[k][c, i - 1] for k in keys}] for i in range(niter_w)]
-            momentums = [] if hmom is None else [[{k: hmom[k][c, i] for k in keys}] for i in range(niter_w)]
-            for i in range(niter_w):
-                if self.verbose and (i % (niter_w / 10) == 0):
-                    print('loss: {0:.4f}'.format(lo[i, c]), file=self.out)
-            results.append((posterior, lo[:, c].copy(), positions, momentums))
+        first = lambda c: {k: before[MLP_PARAM_NAMES.index(k)][c] for k in keys}   # noqa: E731
+        results, traces = self._assemble_chains(
+            C, nburn, niter_w, burn and burn[:3], burn and burn[3], samp,
+            lambda c: {k: host[k][c] for k in keys},
+            lambda c, i: first(c) if i == 0 else {k: host[k][c, i - 1] for k in keys},
+            None if samp is None or hmom is None else lambda c, i: {k: hmom[k][c, i] for k in keys})
         self._note_traces(traces)
         return results
 

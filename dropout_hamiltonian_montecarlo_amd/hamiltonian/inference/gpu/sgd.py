@@ -26,6 +26,8 @@ import torch
 from dropout_hamiltonian_montecarlo_amd import _native as nat
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError, ptr
 
+from . import _mlp_call
+
 
 class sgd:
 
@@ -121,7 +123,6 @@ class sgd:
         negative_log_posterior (sgd.py:42) evaluated on the device behind each epoch's last step.  Dropout
         masks: ``masks='off'`` none; ``mask_provider`` set — injected (one forward per step, two on an epoch's
         last step: gradient forward, then evaluation); else Philox keyed by (seed, chain 0, global_step)."""
-        from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
         m = self.model
         verbose = args.get('verbose', None)
         B = int(batch_size)
@@ -140,27 +141,10 @@ class sgd:
                 raise HmcxError("sgd(mlp): %s has shape %s, expected %s" % (k, tuple(par[k].shape), m.shapes[k]))
         mom = {k: torch.zeros_like(par[k]) for k in par}                  # sgd.py:35
         dev = m.device
-        masks = args.get('masks', None)
-        if masks is not None and masks != 'off':
-            raise ValueError("masks must be None or 'off' (inject masks through mask_provider)")
-        masks_d = None
-        mask_off, eval_off = np.zeros(n_steps, dtype=np.int64), np.zeros(n_steps, dtype=np.int64)
-        if masks == 'off':
-            mode = nat.MLP_MASKS_NONE
-        elif self.mask_provider is not None:
-            mode, n3, chunks, off = nat.MLP_MASKS_FIXED, 3 * B * m.n_mid, [], 0
-            for s in range(n_steps):
-                nf = 2 if want[s] else 1
-                mk = np.asarray(self.mask_provider(self.global_step + s, nf))
-                if mk.shape != (nf, 3, B, m.n_mid):
-                    raise HmcxError("sgd(mlp): mask_provider must return [%d, 3, %d, %d]" % (nf, B, m.n_mid))
-                chunks.append(mk.reshape(-1))
-                mask_off[s], eval_off[s] = off, off + n3
-                off += nf * n3
-            if chunks:
-                masks_d = torch.from_numpy(np.concatenate(chunks)).to(dev, m.dtype)
-        else:
-            mode = nat.MLP_MASKS_PHILOX
+        mode, host_masks, mask_off, eval_off = _mlp_call.mask_plan(args.get('masks', None), self.mask_provider,
+                                                                   self.global_step, 1 + want, B, m.n_mid, "sgd(mlp)")
+        eval_off = np.ascontiguousarray(eval_off[:, 0])                   # one evaluation per step at most
+        masks_d = None if host_masks is None else torch.from_numpy(host_masks).to(dev, m.dtype)
         f64 = dict(dtype=torch.float64, device=dev)
         out_loss = torch.empty(n_steps, **f64)
         ev_loss, ev_ss = torch.empty(epochs, **f64), torch.empty((epochs, 6), **f64)
@@ -175,8 +159,8 @@ class sgd:
         a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
         a.eval_mask_off = eval_off.ctypes.data_as(nat.c_i64p)
         a.seed, a.chain, a.step_base = self.seed, 0, self.global_step & 0xFFFFFFFF
-        for i, k in enumerate(MLP_PARAM_NAMES):
-            a.par.p[i], a.mom.p[i] = par[k].data_ptr(), mom[k].data_ptr()
+        _mlp_call.fill_params(a.par, par)
+        _mlp_call.fill_params(a.mom, mom)
         a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
         ctx = nat.context(dev)
         if n_steps:
@@ -185,10 +169,8 @@ class sgd:
         self.loss_trace = out_loss.cpu().numpy()                          # waits for the call
         el, ss = ev_loss.cpu().numpy(), ev_ss.cpu().numpy()
         del masks_d, Xd, yd
-        loss_val = np.zeros(epochs)
+        loss_val = _mlp_call.nlp_from_eval(m, self.start, el, ss)
         for i in range(epochs):
-            parts = [el[i]] + [ss[i, MLP_PARAM_NAMES.index(k)] for k in self.start]
-            loss_val[i] = m.nlp_from_parts(parts, self.start)
             if verbose and (i % (epochs / 10) == 0):
                 print('loss: {0:.4f}'.format(loss_val[i]), file=self.out)
         self.last_state, self.last_momentum = par, mom

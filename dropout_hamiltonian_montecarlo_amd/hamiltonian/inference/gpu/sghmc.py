@@ -21,6 +21,7 @@ import torch
 from dropout_hamiltonian_montecarlo_amd import _native as nat
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError, ptr
 
+from . import _mlp_call
 from .sgmcmc import RunResult, sgmcmc
 
 
@@ -414,8 +415,7 @@ class sghmc(sgmcmc):
         a = nat.MlpSghmcArgs()
         a.dtype = m.code
         a.B, a.n_in, a.n_mid, a.n_out, a.n_steps = batch_size, m.n_in, m.n_mid, m.n_out, n_steps
-        for i, v in enumerate(self._order):
-            a.order[i] = v
+        a.order[:] = self._order
         a.alpha = m.alpha
         a.X, a.y = ptr(Xd), ptr(yd)
         a.row0 = row0.ctypes.data_as(nat.c_i64p)
@@ -429,8 +429,7 @@ class sghmc(sgmcmc):
         a.masks = ptr(masks_d)
         a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
         a.seed, a.chain, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
-        for i, k in enumerate(MLP_PARAM_NAMES):
-            a.par.p[i] = state[k].data_ptr()
+        _mlp_call.fill_params(a.par, state)
         a.out_A, a.out_accepted = ptr(outs['A']), ptr(out_acc)
         a.out_loss, a.out_nlp, a.out_E = ptr(outs['loss']), ptr(outs['nlp']), ptr(outs['E'])
         a.out_abort = ptr(out_abort)

@@ -36,6 +36,7 @@ import torch
 from dropout_hamiltonian_montecarlo_amd import _native as nat
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError, ptr
 
+from . import _mlp_call
 from .sgmcmc import RunResult, sgmcmc
 
 
@@ -212,17 +213,10 @@ class sgld(sgmcmc):
         return st, (self._mom if self.variant == 'gpu' else None)
 
     # ------------------------------------------------------------------ the dropout MLP
-    @staticmethod
-    def _masks_arg(args):
-        masks = args.get('masks', None)
-        if masks is not None and masks != 'off':
-            raise ValueError("masks must be None or 'off' (inject masks through mask_provider)")
-        return masks == 'off'
-
     def _sample_mlp(self, epochs, burnin, batch_size, rng, args):
         """sgmcmc.sample on the MLP: its loop of one call per epoch, with the draws of ``keep_every`` collected
         from the sampling epochs' calls and the device state / momentum left behind."""
-        self._mlp_masks_off = self._masks_arg(args)
+        self._mlp_masks_off = _mlp_call.masks_off(args.get('masks', None))
         self._mlp_sampling = [int(burnin), 0, []]
         self.device_draws = None
         buf = None
@@ -255,7 +249,6 @@ class sgld(sgmcmc):
         at the updated state under fresh masks) where j % log_every == 0, RunResult.nlp[-1] the epoch-end
         negative_log_posterior; ``evals=False`` (step()) runs neither.  chains > 1: one
         hmcx_mlp_sgld_chains_run on the stacked state, ll / nlp / loss_trace with a trailing chain axis."""
-        from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
         m = self.model
         Xd, yd = data
         dev = m.device
@@ -275,23 +268,9 @@ class sgld(sgmcmc):
             want[-1] |= 2
         n_fwd = 1 + (want & 1) + (want >> 1)
         n_evals = int(n_fwd.sum()) - n_steps
-        masks_d = None
-        mask_off, eval_off = np.zeros(n_steps, dtype=np.int64), np.zeros((n_steps, 2), dtype=np.int64)
-        if self._mlp_masks_off:
-            mode = nat.MLP_MASKS_NONE
-        elif self.mask_provider is not None:
-            mode, n3, chunks, off = nat.MLP_MASKS_FIXED, 3 * B * m.n_mid, [], 0
-            for s in range(n_steps):
-                nf = int(n_fwd[s])
-                mk = np.asarray(self.mask_provider(self.global_step + s, nf))
-                if mk.shape != (nf, 3, B, m.n_mid):
-                    raise HmcxError("sgld(mlp): mask_provider must return [%d, 3, %d, %d]" % (nf, B, m.n_mid))
-                chunks.append(mk.reshape(-1))
-                mask_off[s], eval_off[s, 0], eval_off[s, 1] = off, off + n3, off + 2 * n3
-                off += nf * n3
-            masks_d = torch.from_numpy(np.concatenate(chunks)).to(dev, m.dtype)
-        else:
-            mode = nat.MLP_MASKS_PHILOX
+        mode, host_masks, mask_off, eval_off = _mlp_call.mask_plan(
+            'off' if self._mlp_masks_off else None, self.mask_provider, self.global_step, n_fwd, B, m.n_mid, "sgld(mlp)")
+        masks_d = None if host_masks is None else torch.from_numpy(host_masks).to(dev, m.dtype)
         # keep_every: every k-th sampling step (burn-in calls keep nothing)
         C = self.chains
         draw, want_draw, d0 = None, None, 0
@@ -311,21 +290,19 @@ class sgld(sgmcmc):
                     if nd == 0:
                         want_draw = None
                 smp[1] += n_steps
+        # one chain's outputs are the chain call's with C = 1: [n_steps, C], [n_evals, C], [n_evals, C, 6]
         f64 = dict(dtype=torch.float64, device=dev)
+        out_loss = torch.empty((n_steps, C), **f64)
+        ev_loss, ev_ss = torch.empty((max(n_evals, 1), C), **f64), torch.empty((max(n_evals, 1), C, 6), **f64)
         if C == 1:
-            out_loss = torch.empty(n_steps, **f64)
-            ev_loss, ev_ss = torch.empty(max(n_evals, 1), **f64), torch.empty((max(n_evals, 1), 6), **f64)
             a = nat.MlpSgldArgs()
             a.chain = self.chain
         else:
-            out_loss = torch.empty((n_steps, C), **f64)
-            ev_loss, ev_ss = torch.empty((max(n_evals, 1), C), **f64), torch.empty((max(n_evals, 1), C, 6), **f64)
             a = nat.MlpSgldChainsArgs()
             a.C, a.chain0 = C, self.chain
         a.dtype = m.code
         a.B, a.n_in, a.n_mid, a.n_out, a.n_steps = B, m.n_in, m.n_mid, m.n_out, n_steps
-        for i, v in enumerate(self._order):
-            a.order[i] = v
+        a.order[:] = self._order
         a.variant = 1 if self.variant == 'gpu' else 0
         a.alpha = m.alpha
         a.X, a.y = ptr(Xd), ptr(yd)
@@ -339,17 +316,14 @@ class sgld(sgmcmc):
         a.mask_off = mask_off.ctypes.data_as(nat.c_i64p)
         a.eval_mask_off = eval_off.ctypes.data_as(nat.c_i64p)
         a.seed, a.step_base = self.seed, self.global_step & 0xFFFFFFFF
-        mom = self._momentum(state) if self.variant == 'gpu' else None
-        for i, k in enumerate(MLP_PARAM_NAMES):
-            a.par.p[i] = state[k].data_ptr()
-            if mom is not None:
-                a.mom.p[i] = mom[k].data_ptr()
-            if want_draw is not None:
-                a.draws.p[i] = draw[k][:, d0:].data_ptr() if C > 1 else draw[k].data_ptr()
+        _mlp_call.fill_params(a.par, state)
+        if self.variant == 'gpu':
+            _mlp_call.fill_params(a.mom, self._momentum(state))
         if want_draw is not None:
             a.want_draw = want_draw.ctypes.data_as(nat.c_u8p)
+            _mlp_call.fill_params(a.draws, draw if C == 1 else {k: draw[k][:, d0:] for k in draw})
             if C > 1:
-                a.draw_stride = draw[MLP_PARAM_NAMES[0]].shape[1]
+                a.draw_stride = draw[_mlp_call.MLP_PARAM_NAMES[0]].shape[1]
         a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
         ctx = nat.context(dev)
         if C == 1:
@@ -357,27 +331,22 @@ class sgld(sgmcmc):
         else:
             ctx.check(ctx.lib.hmcx_mlp_sgld_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_chains_run")
         self.global_step += n_steps
-        self.loss_trace = out_loss.cpu().numpy()                          # waits for the call; C > 1: [n_steps, C]
+        shape = (n_steps,) if C == 1 else (n_steps, C)
+        self.loss_trace = out_loss.cpu().numpy().reshape(shape)          # waits for the call
         el, ss = ev_loss.cpu().numpy(), ev_ss.cpu().numpy()
         del noise_d, masks_d
         if want_draw is not None and C == 1:
             smp[2].append(draw)
-        shape = (n_steps,) if C == 1 else (n_steps, C)
-        ll, nlp = np.full(shape, np.nan), np.full(shape, np.nan)
+        ll, nlp = np.full((n_steps, C), np.nan), np.full((n_steps, C), np.nan)
         e = 0
         for s in range(n_steps):
             if want[s] & 1:
                 ll[s] = el[e]
                 e += 1
             if want[s] & 2:
-                for c in range(C):
-                    ec, sc = (el[e], ss[e]) if C == 1 else (el[e, c], ss[e, c])
-                    parts = [ec] + [sc[MLP_PARAM_NAMES.index(k)] for k in self.start]
-                    if C == 1:
-                        nlp[s] = m.nlp_from_parts(parts, self.start)
-                    else:
-                        nlp[s, c] = m.nlp_from_parts(parts, self.start)
+                nlp[s] = _mlp_call.nlp_from_eval(m, self.start, el[e], ss[e])
                 e += 1
+        ll, nlp = ll.reshape(shape), nlp.reshape(shape)
         if self.trace is not None:
             self.trace.extend({'L': 1.0, 'A': 1.0, 'accepted': True, 'eps': float(e_)} for e_ in eps)
         return RunResult(np.ones(n_steps), np.ones(n_steps, dtype=bool), ll, nlp=nlp if evals else None)
@@ -389,15 +358,9 @@ class sgld(sgmcmc):
         d = self.device_draws
         if d is None:
             raise HmcxError("chain_diagnostics: no draws (sample with keep_every)")
-        out = {}
-        for k in (list(d.keys()) if vars is None else list(vars)):
-            t = d[k] if self.chains > 1 else d[k][None]
-            if t.shape[1] < 4:
-                raise HmcxError("chain_diagnostics: needs at least 4 draws per chain, has %d" % t.shape[1])
-            shape = tuple(t.shape[2:])
-            _, sr, es = diagnostics.device_diagnostics(t.reshape(t.shape[0], t.shape[1], -1).to(torch.float64))
-            out[k] = (sr.reshape(shape), es.reshape(shape))
-        return out
+        return diagnostics.draws_diagnostics(
+            {k: d[k] if self.chains > 1 else d[k][None] for k in (list(d.keys()) if vars is None else list(vars))},
+            lambda T: "chain_diagnostics: needs at least 4 draws per chain, has %d" % T)
 
     def _step_mlp(self, state, momentum, rng, args):
         """sgld.step on the MLP: one hmcx_mlp_sgld_run of one step on the given minibatch, no evaluation."""
@@ -408,7 +371,7 @@ class sgld(sgmcmc):
             self._mom = {k: (m._dev(momentum[k]).reshape(m.shapes[k]).contiguous().clone() if momentum is not None
                              else torch.zeros_like(st[k])) for k in self.start}
         off = self._mlp_masks_off
-        self._mlp_masks_off = self._masks_arg(args)
+        self._mlp_masks_off = _mlp_call.masks_off(args.get('masks', None))
         try:
             self._run_mlp(st, data, [0], [self.step_size], rng, data[0].shape[0], evals=False)
         finally:
