@@ -119,6 +119,19 @@ class MlpHmcChainsArgs(ctypes.Structure):
                 ("out_mom", MlpParams)]
 
 
+class MlpSghmcChainsArgs(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("B", c_int), ("n_in", c_int), ("n_mid", c_int), ("n_out", c_int),
+                ("n_steps", c_int), ("C", c_int), ("order", c_int * 6), ("alpha", c_double),
+                ("X", c_void_p), ("y", c_void_p), ("row0", c_i64p), ("eps", c_dblp), ("n_iter", c_i32p),
+                ("u_accept", c_dblp),
+                ("noise_mode", c_int), ("noise", c_void_p), ("noise_off", c_i64p),
+                ("mask_mode", c_int), ("masks", c_void_p), ("mask_off", c_i64p),
+                ("seed", ctypes.c_uint64), ("chain0", ctypes.c_uint32), ("step_base", ctypes.c_uint32),
+                ("par", MlpParams), ("out_A", c_void_p), ("out_accepted", c_void_p), ("out_loss", c_void_p),
+                ("out_nlp", c_void_p), ("out_E", c_void_p),
+                ("want_draw", c_u8p), ("draws", MlpParams), ("draw_stride", ctypes.c_int64)]
+
+
 class MlpPredictiveArgs(ctypes.Structure):
     _fields_ = [("dtype", c_int), ("N", c_int), ("n_in", c_int), ("n_mid", c_int), ("n_out", c_int),
                 ("S", c_int), ("T", c_int), ("mask_mode", c_int), ("path", c_int),
@@ -200,7 +213,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_philox_uniforms", "hmcx_philox_normals", "hmcx_philox_normals_f64",
            "hmcx_softmax_grad", "hmcx_softmax_loglik", "hmcx_softmax_predict", "hmcx_sghmc_run",
            "hmcx_sgld_run", "hmcx_hmc_mvn_run", "hmcx_mlp_masks", "hmcx_mlp_grad", "hmcx_mlp_loss",
-           "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_sgd_run", "hmcx_mlp_sgld_run", "hmcx_mlp_sgld_chains_run", "hmcx_mlp_hmc_chains_run", "hmcx_mlp_predictive", "hmcx_linear_predictive", "hmcx_input_masks", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
+           "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_sgd_run", "hmcx_mlp_sgld_run", "hmcx_mlp_sgld_chains_run", "hmcx_mlp_hmc_chains_run", "hmcx_mlp_sghmc_chains_run", "hmcx_mlp_predictive", "hmcx_linear_predictive", "hmcx_input_masks", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
@@ -281,6 +294,8 @@ def load_library():
             lib.hmcx_mlp_sgld_chains_run.argtypes = [c_void_p, ctypes.POINTER(MlpSgldChainsArgs)]
         if hasattr(lib, "hmcx_mlp_hmc_chains_run"):    # absent in older builds loaded for A/B runs
             lib.hmcx_mlp_hmc_chains_run.argtypes = [c_void_p, ctypes.POINTER(MlpHmcChainsArgs)]
+        if hasattr(lib, "hmcx_mlp_sghmc_chains_run"):  # absent in older builds loaded for A/B runs
+            lib.hmcx_mlp_sghmc_chains_run.argtypes = [c_void_p, ctypes.POINTER(MlpSghmcChainsArgs)]
         if hasattr(lib, "hmcx_mlp_predictive"):
             lib.hmcx_mlp_predictive.argtypes = [c_void_p, ctypes.POINTER(MlpPredictiveArgs)]
         if hasattr(lib, "hmcx_linear_predictive"):     # absent in older builds loaded for A/B runs

@@ -1104,6 +1104,7 @@ int hmcx_mlp_sgd_run(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* a) { HMCX_MLP_RUN(s
 int hmcx_mlp_sgld_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* a) { HMCX_MLP_RUN(sgld, mlp_sgld_t); }
 int hmcx_mlp_sgld_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* a) { HMCX_MLP_RUN(sgld_chains, mlp_sgld_chains_t); }
 int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a) { HMCX_MLP_RUN(hmc_chains, mlp_hmc_chains_t); }
+int hmcx_mlp_sghmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sghmc_chains_args* a) { HMCX_MLP_RUN(sghmc_chains, mlp_sghmc_chains_t); }
 #undef HMCX_MLP_RUN
 
 int hmcx_mlp_predictive(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {

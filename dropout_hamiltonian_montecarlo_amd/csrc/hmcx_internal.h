@@ -271,6 +271,7 @@ template <typename T> int mlp_sgd_t(hmcx_ctx*, const hmcx_mlp_sgd_args*);
 template <typename T> int mlp_sgld_t(hmcx_ctx*, const hmcx_mlp_sgld_args*);
 template <typename T> int mlp_sgld_chains_t(hmcx_ctx*, const hmcx_mlp_sgld_chains_args*);
 template <typename T> int mlp_hmc_chains_t(hmcx_ctx*, const hmcx_mlp_hmc_chains_args*);   // hmcx_mlp_hmc_chains.hip
+template <typename T> int mlp_sghmc_chains_t(hmcx_ctx*, const hmcx_mlp_sghmc_chains_args*);   // hmcx_mlp_hmc_chains.hip
 template <typename T> int mlp_masks_t(hmcx_ctx*, int, int, uint64_t, uint32_t, uint32_t, uint32_t, void*);
 // The predictives' own device buffer (hmcx_ctx::pred_ws, hmcx_mlp_pred.hip): grown to `bytes` (stream-
 // synchronising when it grows) and carved by Bump — two passes, the first with a null base to size it.

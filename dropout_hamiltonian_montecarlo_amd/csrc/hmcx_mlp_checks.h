@@ -202,6 +202,27 @@ inline MlpCheck hmc_chains(const hmcx_mlp_hmc_chains_args* a, Who who = "mlp hmc
                                a->mask_mode == HMCX_MLP_MASKS_FIXED ? a->mask_off : nullptr));
   return draw_stride(who, a->n_steps, a->want_draw, a->draw_stride);
 }
+// no evaluation outputs: the modes and their buffers one by one.  chain_step_scan's n_iter limit (6n + 3 below 2^31)
+// is two forwards stricter than this call's last forward, 6n + 1
+inline MlpCheck sghmc_chains(const hmcx_mlp_sghmc_chains_args* a, Who who = "mlp sghmc chains: ") {
+  HMCX_MLP_TRY(head(a, who));
+  HMCX_MLP_TRY(chains_and_wraps(who, a->C, a->chain0, a->step_base, a->n_steps));
+  HMCX_MLP_TRY(param_limit(who, a->n_in, a->n_mid, a->n_out));
+  if (!a->X || !a->y || !a->row0 || !a->eps || !a->n_iter || !a->u_accept || !params_ok(&a->par) || !a->out_A ||
+      !a->out_accepted || !a->out_loss)
+    return einval(who, "null pointer");
+  HMCX_MLP_TRY(noise_mode(who, a->noise_mode));
+  HMCX_MLP_TRY(noise_buffers(who, a->noise_mode, a->noise, a->noise_off));
+  HMCX_MLP_TRY(mask_mode(who, a->mask_mode));
+  HMCX_MLP_TRY(mask_buffers(who, a->mask_mode, a->masks, a->mask_off));
+  HMCX_MLP_TRY(draw_outputs(who, a->want_draw, &a->draws));
+  HMCX_MLP_TRY(order_permutation(who, a->order));
+  HMCX_MLP_TRY(step_scan(who, a->n_steps, a->row0, nullptr, nullptr));
+  HMCX_MLP_TRY(chain_step_scan(who, (int64_t)a->n_steps * a->C, a->n_iter,
+                               a->noise_mode == HMCX_NOISE_BUFFER ? a->noise_off : nullptr,
+                               a->mask_mode == HMCX_MLP_MASKS_FIXED ? a->mask_off : nullptr));
+  return draw_stride(who, a->n_steps, a->want_draw, a->draw_stride);
+}
 // the context-free part of hmcx_mlp_predictive; the fused path's eligibility needs the context and follows it
 inline MlpCheck predictive(const hmcx_mlp_predictive_args* a, Who who = "mlp predictive: ") {
   if (!a) return einval("", "null args");

@@ -11,7 +11,19 @@ The whole trajectory of every step runs inside libhmcx (hmcx_sghmc_run): one cha
 persistent launch per call (csrc/hmcx_persist2.hip); C ≥ 16 chains — the chain-batched GEMMs
 (csrc/hmcx_batch.h); otherwise one k_fwd + one k_grad launch per leapfrog iteration.  The host only
 prepares the per-step schedule and reads back the per-step scalars.
+
+The dropout MLP: one chain — hmcx_mlp_sghmc_run, one call per epoch (``_run_mlp``).  Several chains (``chains=C``,
+1 < C ≤ 64, ``noise='philox'``): one hmcx_mlp_sghmc_chains_run per epoch, the chains as the problems of batched
+launches (groups of at most 6) on shared minibatches, each chain with its own Philox momenta, noise, masks, path
+lengths and accept uniforms (``nat.philox_schedule``: chain c is the one-chain stream of ``chain + c``).
+``start_p[var]`` is the variable's shape (every chain starts there) or ``[C, *shape]``; the device state and
+``last_state`` are ``[C, *shape]``, ``posterior[var]`` is ``[C, epochs, *shape]``, ``logp`` ``[C, epochs]``, the
+trace records hold ``[C]`` arrays and ``keep_every=k`` leaves every k-th sampling step in ``device_draws[var]``
+``[C, T, *shape]`` (one buffer, written in place; what ``mlp.posterior_predictive`` and ``chain_diagnostics`` read).
+``sample(..., masks='off')`` runs the chains without dropout.  The host noise stream and ``mask_provider`` would feed
+every chain the same values, and ``step()`` is the reference's one-chain call: all three raise with ``chains > 1``.
 """
+import ctypes
 import os
 import time
 
@@ -40,15 +52,47 @@ class sghmc(sgmcmc):
 
     mask_provider = None    # MLP parity hook: f(global_step, n_forwards) -> [n_fwd, 3, B, n_mid] masks
 
+    def __init__(self, model, start_p, path_length=1.0, step_size=0.1, verbose=True,
+                 noise='numpy', seed=0, chain=0, chains=1, keep_every=None):
+        if keep_every is not None and int(keep_every) < 1:
+            raise ValueError("keep_every must be None or >= 1")
+        self.keep_every = None if keep_every is None else int(keep_every)   # MLP, chains > 1: device_draws
+        self.device_draws = None
+        self._mlp_masks_off = False
+        self._mlp_sampling = None          # inside sample(), MLP chains: [burn-in calls left, sampling steps done]
+        self._mlp_draw_buf = None          # inside sample(), MLP chains: the [C, T, *shape] draw buffers
+        super().__init__(model, start_p, path_length=path_length, step_size=step_size, verbose=verbose,
+                         noise=noise, seed=seed, chain=chain, chains=chains)
+
     def _check_vars(self):
         if self.model._hmcx_model == 'mlp':
             from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
             if sorted(self.start.keys()) != sorted(MLP_PARAM_NAMES):
                 raise HmcxError("sghmc(mlp): start_p must hold exactly %s" % (MLP_PARAM_NAMES,))
-            if self.chains != 1:
-                raise HmcxError("sghmc(mlp): one chain per sampler (chains=1)")
+            C = self.chains
+            if C > 64:
+                raise HmcxError("sghmc(mlp): at most 64 chains per sampler")
+            if C > 1 and self.noise == 'numpy':
+                # the host stream would replay one sequence of momenta, noise, path lengths and uniforms in every chain
+                raise HmcxError("sghmc(mlp): chains=%d draws every chain's momenta, noise and schedule from Philox "
+                                "streams (chain + c); noise='numpy' would replay one host stream in every chain: "
+                                "use noise='philox'" % C)
+            if C == 1 and self.keep_every is not None:
+                raise HmcxError("sghmc(mlp): keep_every keeps the draws of the multi-chain call (chains > 1); "
+                                "one-chain device draws are not implemented")
+            for k in self.start:
+                shape, want = tuple(self.start[k].shape), self.model.shapes[k]
+                if C > 1 and shape != want and shape != (C,) + want:
+                    raise HmcxError("sghmc(mlp): %s has shape %s, expected %s or %s" % (k, shape, want, (C,) + want))
             self._order = [MLP_PARAM_NAMES.index(k) for k in self.start.keys()]
+            if C > 1:
+                # one start per chain, [C, *shape]; self.start keeps the per-chain shapes (chain 0's values)
+                self._mlp_start = {k: np.array(np.broadcast_to(v, (C,) + self.model.shapes[k]))
+                                   for k, v in self.start.items()}
+                self.start = {k: v[0] for k, v in self._mlp_start.items()}
             return
+        if self.keep_every is not None:
+            raise HmcxError("sghmc: keep_every is the dropout MLP's multi-chain route (mlp model, chains > 1)")
         if self.model._hmcx_model != 'softmax' or list(self.start.keys()) != ['weights', 'bias']:
             raise HmcxError("sghmc: libhmcx implements the softmax model with start_p keys "
                             "['weights', 'bias'] (in that order, sghmc.py:29)")
@@ -385,9 +429,125 @@ class sghmc(sgmcmc):
             x['recovered'] = True
         torch.cuda.synchronize()
 
+    # ------------------------------------------------------------------ several MLP chains
+    def _mlp_chains(self):
+        return self.model._hmcx_model == 'mlp' and self.chains > 1
+
+    def _init_state(self):
+        if not self._mlp_chains():
+            return super()._init_state()
+        dt, dev = self.model.dtype, self.model.device
+        return {k: torch.as_tensor(v).to(dev, dt).contiguous().clone() for k, v in self._mlp_start.items()}
+
+    def _state_to_host(self, state):
+        if not self._mlp_chains():
+            return super()._state_to_host(state)
+        return {k: state[k].detach().cpu().numpy().astype(np.float64) for k in self.start}   # [C, *shape]
+
+    def sample(self, epochs=1, burnin=1, batch_size=1, rng=None, **args):
+        if not self._mlp_chains():
+            return super().sample(epochs=epochs, burnin=burnin, batch_size=batch_size, rng=rng, **args)
+        if self.mask_provider is not None:
+            raise HmcxError("sghmc(mlp): mask_provider feeds one chain's masks (a parity hook); with chains=%d every "
+                            "chain draws its own Philox masks, or none (masks='off')" % self.chains)
+        self._mlp_masks_off = _mlp_call.masks_off(args.get('masks', None))
+        self._mlp_sampling = [int(burnin), 0]
+        self.device_draws = None
+        buf = None
+        if self.keep_every is not None:
+            # the draws of every chain in one buffer [C, T, *shape] the calls write in place
+            n_rows = len(range(0, args['X_train'].shape[0] - int(batch_size) + 1, int(batch_size)))
+            T = int(epochs) * n_rows // self.keep_every
+            buf = {k: torch.empty((self.chains, T) + self.model.shapes[k], dtype=self.model.dtype,
+                                  device=self.model.device) for k in self.start}
+        self._mlp_draw_buf = buf
+        try:
+            out = super().sample(epochs=epochs, burnin=burnin, batch_size=batch_size, rng=rng, **args)
+        finally:
+            self._mlp_sampling = None
+            self._mlp_masks_off = False
+            self._mlp_draw_buf = None
+        self.device_draws = buf
+        return out
+
+    def _run_mlp_chains(self, state, data, rows, eps, batch_size):
+        """len(rows) steps of the C chains as one hmcx_mlp_sghmc_chains_run on the stacked state [C, *shape]; the
+        RunResult's arrays carry a trailing chain axis ([n_steps, C]; E [n_steps, C, 2])."""
+        m, C = self.model, self.chains
+        Xd, yd = data
+        dev = m.device
+        n_steps = len(rows)
+        n_iter, u, _, _ = self._schedule(n_steps, eps, None, 0)          # Philox: [n_steps, C] each
+        n_iter, u = np.ascontiguousarray(n_iter.reshape(-1)), np.ascontiguousarray(u.reshape(-1))
+        row0 = np.asarray(rows, dtype=np.int64)
+        eps_a = np.asarray(eps, dtype=np.float64)
+        # keep_every: every k-th sampling step (burn-in calls keep nothing)
+        want_draw, d0 = None, 0
+        smp = self._mlp_sampling
+        if smp is not None:
+            if smp[0] > 0:
+                smp[0] -= 1
+            else:
+                if self.keep_every is not None:
+                    idx = smp[1] + np.arange(n_steps)
+                    want_draw = ((idx + 1) % self.keep_every == 0).astype(np.uint8)
+                    d0 = smp[1] // self.keep_every
+                    if not want_draw.any():
+                        want_draw = None
+                smp[1] += n_steps
+        f64 = dict(dtype=torch.float64, device=dev)
+        outs = {k: torch.empty((n_steps, C) + w, **f64) for k, w in (('A', ()), ('loss', ()), ('nlp', ()), ('E', (2,)))}
+        out_acc = torch.empty((n_steps, C), dtype=torch.int32, device=dev)
+        a = nat.MlpSghmcChainsArgs()
+        a.dtype = m.code
+        a.B, a.n_in, a.n_mid, a.n_out, a.n_steps, a.C = int(batch_size), m.n_in, m.n_mid, m.n_out, n_steps, C
+        a.order[:] = self._order
+        a.alpha = m.alpha
+        a.X, a.y = ptr(Xd), ptr(yd)
+        a.row0 = row0.ctypes.data_as(nat.c_i64p)
+        a.eps = eps_a.ctypes.data_as(nat.c_dblp)
+        a.n_iter = n_iter.ctypes.data_as(nat.c_i32p)
+        a.u_accept = u.ctypes.data_as(nat.c_dblp)
+        a.noise_mode = nat.NOISE_PHILOX
+        a.mask_mode = nat.MLP_MASKS_NONE if self._mlp_masks_off else nat.MLP_MASKS_PHILOX
+        a.seed, a.chain0, a.step_base = self.seed, self.chain, self.global_step & 0xFFFFFFFF
+        _mlp_call.fill_params(a.par, state)
+        a.out_A, a.out_accepted = ptr(outs['A']), ptr(out_acc)
+        a.out_loss, a.out_nlp, a.out_E = ptr(outs['loss']), ptr(outs['nlp']), ptr(outs['E'])
+        if want_draw is not None:
+            draw = self._mlp_draw_buf
+            a.want_draw = want_draw.ctypes.data_as(nat.c_u8p)
+            _mlp_call.fill_params(a.draws, {k: draw[k][:, d0:] for k in draw})
+            a.draw_stride = draw[_mlp_call.MLP_PARAM_NAMES[0]].shape[1]
+        ctx = nat.context(dev)
+        ctx.check(ctx.lib.hmcx_mlp_sghmc_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sghmc_chains_run")
+        self.global_step += n_steps
+        h = {k: v.cpu().numpy() for k, v in outs.items()}               # waits for the call
+        res = RunResult(h['A'], out_acc.cpu().numpy().astype(bool), h['loss'], h['E'], nlp=h['nlp'])
+        if self.trace is not None:
+            for s in range(n_steps):
+                t = self.trace[len(self.trace) - n_steps + s]
+                t['A'] = res.A[s].copy()
+                t['accepted'] = res.accepted[s].copy()
+                t['E'] = res.E[s].copy()                   # [C, 2]: (E_current, E_new) of the accept test
+        return res
+
+    def chain_diagnostics(self, vars=None):
+        """{var: (split_rhat, ess)} of the kept draws (``device_draws``, [C, T, *shape]), each of the variable's
+        shape, computed on the device one variable at a time (diagnostics.device_diagnostics)."""
+        from dropout_hamiltonian_montecarlo_amd import diagnostics
+        d = self.device_draws
+        if d is None:
+            raise HmcxError("chain_diagnostics: no draws (sample the MLP with chains > 1 and keep_every)")
+        return diagnostics.draws_diagnostics(
+            {k: d[k] for k in (list(d.keys()) if vars is None else list(vars))},
+            lambda T: "chain_diagnostics: needs at least 4 draws per chain, has %d" % T)
+
     def _run_mlp(self, state, data, rows, eps, rng, batch_size):
         """MLP steps through hmcx_mlp_sghmc_run (hmcx_mlp.hip): same schedule and noise layout as the
         softmax path; dropout masks from Philox on the device, or from ``mask_provider`` (parity)."""
+        if self.chains > 1:
+            return self._run_mlp_chains(state, data, rows, eps, batch_size)
         from dropout_hamiltonian_montecarlo_amd.hamiltonian.models.gpu.mlp import MLP_PARAM_NAMES
         m = self.model
         Xd, yd = data

@@ -857,6 +857,81 @@ typedef struct hmcx_mlp_hmc_chains_args {
 } hmcx_mlp_hmc_chains_args;
 int hmcx_mlp_hmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* a);
 
+/* SGHMC on the MLP, n_steps steps of C chains in one call (extension; the reference runs one chain per process):
+ * replaces hamiltonian/inference/cpu/sghmc.py:19-39 with the A1 completion, exactly as hmcx_mlp_sghmc_run defines it,
+ * for every (step s, chain c).  All chains share the minibatch rows row0[s] .. row0[s] + B and ε = eps[s]; n =
+ * n_iter[s·C + c] and u = u_accept[s·C + c] are the chain's own:
+ *   1. momentum: p = P standard normals laid out variable after variable in `order` (element e = the variable's
+ *      offset in that layout + its index).  HMCX_NOISE_BUFFER: noise[noise_off[s·C + c] + e] (double, converted to
+ *      dtype); HMCX_NOISE_PHILOX: the Philox normal of (seed, chain0 + c, step_base + s, slot 0, e) in dtype.  The
+ *      trajectory works on a copy q' ← q.
+ *   2. trajectory: for it = 0 .. n − 1 and i = 0 .. 5, v = order[i]:  q'_v += ε·p_v;  g_v = the v component of
+ *      hmcx_mlp_grad at q' (∇ mean CE + ½·alpha·θ) under forward f = 6·it + i;  p_v = ((1 − ε)·p_v + ε·g_v) + (2ε)·z,
+ *      each product and sum rounded once in dtype (the statements of the one-chain call's update).  z: BUFFER
+ *      noise[noise_off[s·C + c] + P·(it + 1) + e], PHILOX slot it + 1, element e.  No momentum negation; the dead
+ *      gradient of sghmc.py:26 is not executed.  Only component v of an evaluation is computed, the layer-1 output is
+ *      reused until W1 moves.
+ *   3. forward 6n is the proposal's energy forward, forward 6n + 1 the current state's (hmcx_mlp_sghmc_run's
+ *      numbering).  n = 0 keeps the numbering and A still comes from the two forwards: under dropout it is not 1.
+ *      Masks of forward f: HMCX_MLP_MASKS_NONE no dropout; FIXED masks + mask_off[s·C + c] + f·3·B·n_mid (dtype;
+ *      each chain its own block); PHILOX what hmcx_mlp_masks(seed, chain0 + c, step_base + s, 0x80000000 + f) writes.
+ *   4. energies: E = (loss + log_prior) + ½Σp², loss the mean CE of the forward, log_prior = −Σ_v ½·alpha·Σθ_v²/dim_v
+ *      and the kinetic term both over `order`, in float64 with a fixed summation order.
+ *   5. A = min(1, exp(E_cur − E_new)) as Python's min (NaN gives 1); accepted = isfinite(A) && u < A; an accepted
+ *      step commits q' to par.
+ * Outputs at index s·C + c: out_A, out_accepted, out_E [·][2] = (E_current, E_new), out_loss = the mean CE of the
+ * kept state under that state's energy forward, out_nlp = loss + log_prior of the kept state.  Where want_draw[s] is
+ * set, the d-th such step of chain c stores the kept state at draws.p[v] + (c·draw_stride + d)·n_v.
+ * Guarantees:
+ *   chains   with PHILOX noise and masks chain c is bit for bit the C = 1 call with chain0 + c — state, A, E, flags,
+ *            loss, nlp, draws, float64 and float32: a chain's result depends neither on C, nor on how the chains
+ *            are grouped into launches, nor on the other chains' path lengths.
+ *   splits   one call of n steps equals any split into calls that carry par and advance step_base (and the host
+ *            arrays and the draw pointers), bit for bit.
+ *   errors   invalid arguments return a negative code, set hmcx_last_error, launch nothing and leave par
+ *            untouched: C outside 1 .. 64, order not a permutation, n_iter < 0 or so large that the forward number
+ *            0x80000000 + 6n + 1 wraps, chain0 + C or step_base + n_steps wrapping 2^32, want_draw with draw_stride
+ *            below the call's flagged steps, a missing buffer for the chosen modes; NULL ctx or args: −1.
+ *   n_steps == 0 does nothing.
+ * Against hmcx_mlp_sghmc_run: the same values up to the summation order inside the forwards (other GEMM launches);
+ * the one-chain call stays the fused, faster path for one chain.
+ * Schedule: the chains are the problems of batched launches, in groups of at most 6; a group takes all steps of the
+ * call before the next group starts.  Evaluation f of a step is launched for the chains of the group that still
+ * have one, so a ragged step costs max_c(6·n_c) evaluations per group.  Only unfused launches: no cross-workgroup
+ * exchange, no spin-wait, no abort word.  Nothing is read back inside the call.  Stream-ordered; returns once
+ * enqueued. */
+typedef struct hmcx_mlp_sghmc_chains_args {
+  int dtype;
+  int B, n_in, n_mid, n_out, n_steps;
+  int C;                      /* chains, 1 .. 64 */
+  int order[6];               /* canonical variable indices 0=W1 .. 5=b3 in the caller's start order */
+  double alpha;
+  const void* X;              /* device [N][n_in] */
+  const int32_t* y;           /* device [N] labels */
+  const int64_t* row0;        /* host [n_steps] */
+  const double* eps;          /* host [n_steps] */
+  const int32_t* n_iter;      /* host [n_steps*C] */
+  const double* u_accept;     /* host [n_steps*C] */
+  int noise_mode;             /* HMCX_NOISE_BUFFER or HMCX_NOISE_PHILOX */
+  const double* noise;        /* device, BUFFER */
+  const int64_t* noise_off;   /* host [n_steps*C], BUFFER: P·(n + 1) normals each */
+  int mask_mode;              /* HMCX_MLP_MASKS_NONE / _FIXED / _PHILOX */
+  const void* masks;          /* device (dtype), FIXED */
+  const int64_t* mask_off;    /* host [n_steps*C], FIXED: forward f of (s, c) at + f·3·B·n_mid */
+  uint64_t seed;
+  uint32_t chain0, step_base; /* chain c draws under Philox chain chain0 + c */
+  hmcx_mlp_params par;        /* [C][shape_v] per variable, updated in place */
+  double* out_A;              /* device [n_steps*C] */
+  int32_t* out_accepted;      /* device [n_steps*C] */
+  double* out_loss;           /* device [n_steps*C] */
+  double* out_nlp;            /* device [n_steps*C] or NULL */
+  double* out_E;              /* device [n_steps*C][2] or NULL */
+  const uint8_t* want_draw;   /* host [n_steps] or NULL */
+  hmcx_mlp_params draws;      /* device, [C][draw_stride][shape_v] per variable (read where want_draw is given) */
+  int64_t draw_stride;        /* draws per chain of the caller's buffers */
+} hmcx_mlp_sghmc_chains_args;
+int hmcx_mlp_sghmc_chains_run(hmcx_ctx* ctx, const hmcx_mlp_sghmc_chains_args* a);
+
 /* Posterior predictive of the MLP on the device (extension; the reference's predict, mlp.py:84-96, is one
  * parameter set and one mask draw per call).  D = S·T draws, draw d = s·T + t: parameter set s (par.p[i]
  * holds S stacked copies, [S][shape_i], contiguous) under dropout draw t.  z_d = net(X; θ_s, masks_d) by the
