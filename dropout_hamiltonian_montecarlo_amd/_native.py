@@ -7,6 +7,7 @@ libamdhip64.so.7 satisfies libhmcx.so's NEEDED entry by soname).
 """
 import atexit
 import ctypes
+import math
 import os
 import threading
 
@@ -205,6 +206,21 @@ class MhMvnArgs(ctypes.Structure):
 MODEL_SOFTMAX, MODEL_LOGISTIC = 0, 1
 MLP_MASK_SLOT0 = 0x80000000
 MLP_MASKS_NONE, MLP_MASKS_FIXED, MLP_MASKS_PHILOX = 0, 1, 2
+MLP_DROPOUT_DEFAULT = 0.1
+
+
+def mlp_dropout_threshold(ratio):
+    """The 24-bit keep threshold ceil(ratio * 2^24) of a dropout ratio of the MLP (csrc/hmcx_keep_law.h
+    keep_threshold, hmcx_set_mlp_dropout's rule: 0 <= ratio and the threshold below 2^24); ValueError for a ratio
+    that has none.  Host arithmetic only."""
+    try:
+        r = float(ratio)
+        t = math.ceil(r * 16777216.0) if r >= 0.0 else -1          # NaN compares false; inf raises
+    except (TypeError, ValueError, OverflowError):
+        t = -1
+    if not 0 <= t < 16777216:
+        raise ValueError("mlp dropout: ratio must satisfy 0 <= ratio and ceil(ratio * 2^24) < 2^24, got %r" % (ratio,))
+    return t
 
 
 # Every symbol include/hmcx.h declares (checked by tests/test_capi.py).
@@ -216,6 +232,7 @@ EXPORTS = ("hmcx_version", "hmcx_create", "hmcx_destroy", "hmcx_last_error", "hm
            "hmcx_mlp_sghmc_run", "hmcx_mlp_hmc_leapfrog", "hmcx_mlp_sgd_run", "hmcx_mlp_sgld_run", "hmcx_mlp_sgld_chains_run", "hmcx_mlp_hmc_chains_run", "hmcx_mlp_sghmc_chains_run", "hmcx_mlp_predictive", "hmcx_linear_predictive", "hmcx_input_masks", "hmcx_logistic_grad", "hmcx_logistic_loglik", "hmcx_logistic_predict",
            "hmcx_sumsq", "hmcx_sgd_run", "hmcx_hmc_run", "hmcx_hmc_chains_run", "hmcx_mh_run", "hmcx_mh_mvn_run", "hmcx_axpy", "hmcx_mvn_eval",
            "hmcx_clear_abort", "hmcx_get_recoveries", "hmcx_note_recovery", "hmcx_get_mlp_forward_counts", "hmcx_set_sgld_fuse", "hmcx_philox_schedule", "hmcx_host_wait", "hmcx_set_mlp_fuse",
+           "hmcx_set_mlp_dropout", "hmcx_get_mlp_dropout",
            "hmcx_comm_unique_id", "hmcx_comm_init", "hmcx_comm_destroy", "hmcx_allgather_chain_stats",
            "hmcx_allreduce_f64", "hmcx_chain_diagnostics", "hmcx_p2_plan_query", "hmcx_p2_ahead_query",
            "hmcx_set_sghmc_ahead", "hmcx_sghmc_ahead_note", "hmcx_p2_ahead_rule", "hmcx_sghmc_batch_plan_query",
@@ -303,6 +320,8 @@ def load_library():
             lib.hmcx_input_masks.argtypes = [c_void_p, c_int, c_int, c_double, u64, u32, u32, c_void_p]
         if hasattr(lib, "hmcx_set_mlp_fuse"):          # absent in older builds loaded for A/B runs
             lib.hmcx_set_mlp_fuse.argtypes = [c_void_p, c_int]
+        lib.hmcx_set_mlp_dropout.argtypes = [c_void_p, c_double]
+        lib.hmcx_get_mlp_dropout.argtypes = [c_void_p, ctypes.POINTER(c_double)]
         if hasattr(lib, "hmcx_set_sgld_fuse"):
             lib.hmcx_set_sgld_fuse.argtypes = [c_void_p, c_int]
         if hasattr(lib, "hmcx_comm_init"):
@@ -461,6 +480,24 @@ class Context:
         """Fused layer-2/3 MLP launches in the sampler (include/hmcx.h hmcx_set_mlp_fuse)."""
         self.check(self.lib.hmcx_set_mlp_fuse(self.h, 1 if on else 0), "hmcx_set_mlp_fuse")
         self.mlp_fuse = bool(on)
+
+    mlp_dropout = MLP_DROPOUT_DEFAULT     # the ratio this wrapper last set (a new context's default)
+
+    def set_mlp_dropout(self, ratio):
+        """The ratio of the Philox dropout masks this context draws from now on (include/hmcx.h
+        hmcx_set_mlp_dropout); an invalid ratio raises and leaves it as it was.  The value last set is kept here, so
+        setting it again costs no library call."""
+        ratio = float(ratio)
+        if ratio == self.mlp_dropout:
+            return
+        self.check(self.lib.hmcx_set_mlp_dropout(self.h, ratio), "hmcx_set_mlp_dropout")
+        self.mlp_dropout = ratio
+
+    def get_mlp_dropout(self):
+        """The ratio the library holds (include/hmcx.h hmcx_get_mlp_dropout)."""
+        out = c_double()
+        self.check(self.lib.hmcx_get_mlp_dropout(self.h, ctypes.byref(out)), "hmcx_get_mlp_dropout")
+        return out.value
 
     def set_timing(self, on):
         """Bracket every sampler run's kernels with HIP events on the launch stream (resets totals)."""

@@ -691,6 +691,24 @@ int hmcx_set_mlp_fuse(hmcx_ctx* ctx, int on) {
   return HMCX_OK;
 }
 
+int hmcx_set_mlp_dropout(hmcx_ctx* ctx, double ratio) {
+  HMCX_GUARD_CTX(ctx);
+  KeepLaw law;
+  double scale;
+  const char* msg = nullptr;
+  if (int rc = keep_law_of(ratio, &law, &scale, &msg)) return set_error(ctx, rc, msg);
+  ctx->mlp_dropout = ratio;
+  ctx->mlp_keep = law;
+  ctx->mlp_scale = scale;
+  return HMCX_OK;
+}
+
+int hmcx_get_mlp_dropout(const hmcx_ctx* ctx, double* ratio) {
+  if (!ctx || !ratio) return HMCX_EINVAL;
+  *ratio = ctx->mlp_dropout;
+  return HMCX_OK;
+}
+
 int hmcx_set_sgld_fuse(hmcx_ctx* ctx, int on) {
   HMCX_GUARD_CTX(ctx);
   ctx->wide_nofuse = on ? 0 : 1;

@@ -6,6 +6,7 @@
 #include <vector>
 #include <algorithm>
 #include "hmcx.h"
+#include "hmcx_keep_law.h"
 
 struct hmcx_ctx {
   int device = 0;
@@ -71,6 +72,10 @@ struct hmcx_ctx {
   int* mlp_abort_dev = nullptr;
   int mlp_nofuse = 0;                  // hmcx_set_mlp_fuse(ctx, 0): the sampler runs unfused
   int wide_nofuse = 0;                 // hmcx_set_sgld_fuse(ctx, 0): wide SGLD on the three launches
+  // the ratio of every Philox dropout mask of the MLP (hmcx_set_mlp_dropout), its keep law and 1 / (1 − ratio)
+  double mlp_dropout = hmcx::MLP_DROPOUT_DEFAULT;
+  hmcx::KeepLaw mlp_keep = hmcx::KEEP_LAW_DEFAULT;
+  double mlp_scale = 1.0 / (1.0 - hmcx::MLP_DROPOUT_DEFAULT);
   // fused wide-SGLD forward + softmax (hmcx_wide.hip k_wfwd_sm): its own abort word, never the
   // persistent SGHMC kernels' sticky one — read and lowered only by the wide call that raised it
   int* wide_abort_dev = nullptr;
@@ -94,6 +99,8 @@ constexpr double CLIP_HI = 0x1.205966f2b4f12p+5;    //  36.04365338911715
 constexpr double CLIP_LO = -0x1.6232bdd7abcd2p+9;   // -708.3964185322641
 
 int set_error(hmcx_ctx* ctx, int code, const std::string& msg);
+// The context's dropout law as a kernel computing in T takes it (by value, in its argument block).
+template <typename T> inline DropLaw<T> drop_law(const hmcx_ctx* ctx) { return DropLaw<T>{ctx->mlp_keep, (T)ctx->mlp_scale}; }
 
 // Kernel timing: timing_begin/timing_end record events on `st` around a run's kernels;
 // timing_collect folds a finished interval into (t_ms, t_n).  No-ops while timing is off.

@@ -20,8 +20,8 @@ namespace hmcx {
 // The static kernels only this unit launches (a static kernel is emitted by every unit that sees it).
 // The keep flags alone (the forwards a k_fwdr step left undrawn when it falls back to the k_mm forwards).
 static __global__ __launch_bounds__(256) void k_mlp_keep(uint32_t* keep, int n3, KeepRange kr, uint64_t seed, uint32_t chain,
-                                                  uint32_t step) {
-  keep_flags(keep, n3, kr, seed, chain, step, (size_t)blockIdx.x * 256 + threadIdx.x);
+                                                  uint32_t step, KeepLaw law) {
+  keep_flags(law, keep, n3, kr, seed, chain, step, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // MH accept (hmc.py:67-79): E = nlp + ½Σp², nlp = loss + log_prior, log_prior = −Σ_v ½α·Σθ²/dim.
@@ -850,7 +850,7 @@ int mlp_masks_t(hmcx_ctx* ctx, int B, int n_mid, uint64_t seed, uint32_t chain, 
                 void* out) {
   const int n3 = 3 * B * n_mid;
   hipLaunchKernelGGL(k_mlp_masks<T>, dim3((unsigned)(((n3 + 63) / 64 + 255) / 256)), dim3(256), 0, ctx->stream,
-                     (T*)out, n3, seed, chain, step, slot);
+                     drop_law<T>(ctx), (T*)out, n3, seed, chain, step, slot);
   HMCX_HIP(ctx, hipGetLastError());
   return HMCX_OK;
 }
@@ -914,7 +914,7 @@ int mlp_leapfrog_t(hmcx_ctx* ctx, const hmcx_mlp_leapfrog_args* s) {
     }
     if (masks && pmasks) {
       k.masks = (T*)s->masks; k.n3 = 3 * s->B * s->n_mid; k.seed = s->seed; k.chain = s->chain; k.step = s->step;
-      k.slot = slot++;
+      k.slot = slot++; k.law = drop_law<T>(ctx);
       n = std::max(n, (int64_t)(k.n3 + 63) / 64);
     }
     // the previous call's deferred bias / W3 gradients: the launch applies those its kicks read (g of pu or
@@ -972,6 +972,7 @@ int mlp_sgd_t(hmcx_ctx* ctx, const hmcx_mlp_sgd_args* s) {
   MlpNet<T>& net = f.net;
   T* q[6];
   MlpSgd<T> k{};
+  k.law = drop_law<T>(ctx);
   for (int v = 0; v < 6; ++v) {
     q[v] = (T*)s->par.p[v];
     k.vt.q[v] = q[v]; k.vt.p[v] = s->mom.p[v]; k.vt.qn[v] = f.g[v]; k.vt.n[v] = net.nvar(v);
@@ -1015,6 +1016,7 @@ int mlp_sgld_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_args* s) {
   if (int rc = timing_begin(ctx, ctx->stream)) return rc;
   T* q[6];
   MlpSgld<T> k{};
+  k.law = drop_law<T>(ctx);
   for (int v = 0; v < 6; ++v) {
     q[v] = (T*)s->par.p[v];
     k.vt.q[v] = q[v]; k.vt.p[v] = s->variant == 1 ? s->mom.p[v] : nullptr; k.vt.qn[v] = f.g[v]; k.vt.n[v] = net.nvar(v);
@@ -1145,7 +1147,7 @@ struct MlpSghmc {
     bool e_done[2] = {false, false}, e_fr[2] = {false, false};
     // masks of forward f of the step: its stored keep flags (Philox), or the caller's values
     MaskSrc<T> masks_for(int f) const {
-      const T scale = (T)(1.0 / 0.9);
+      const T scale = (T)c->ctx->mlp_scale;
       if (c->philox_masks) return MaskSrc<T>{nullptr, c->keep + (size_t)f * c->kw, scale, c->mn};
       return MaskSrc<T>{(const T*)c->s->masks + c->s->mask_off[si] + (size_t)f * c->n3, nullptr, scale, c->mn};
     }
@@ -1327,7 +1329,7 @@ struct MlpSghmc {
       const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);      // one keep group per thread
       const unsigned rows = (unsigned)((items + (size_t)NPART * 256 - 1) / ((size_t)NPART * 256));
       hipLaunchKernelGGL(k_mlp_start<T>, dim3(NPART, 6 + rows), dim3(256), 0, stream, vt, (T)st.eps, drift, s->noise_mode,
-                         st.nz, s->seed, s->chain, st.step_id, part_cur, prev_acc, keep, n3, kr);
+                         st.nz, s->seed, s->chain, st.step_id, part_cur, prev_acc, keep, n3, kr, ctx->mlp_keep);
     } else {
       hipLaunchKernelGGL(k_mlp_init<T>, dim3(NPART, 6), dim3(256), 0, stream, vt, (T)st.eps, drift, s->noise_mode, st.nz,
                          s->seed, s->chain, st.step_id, part_cur, prev_acc);
@@ -1401,8 +1403,15 @@ struct MlpSghmc {
     if (x.it == 0) fa[na++] = energy_ride(st, 1, xpar);
     RbFwdArgs<T> kf{};                                         // the next iteration's flags, in k_fwdr's free rows
     if (st.keep_split && !x.last) {
-      kf.keep = keep; kf.n3 = n3; kf.kr = KeepRange{6, 6 * (x.it + 1), 6, 0};
-      kf.seed = s->seed; kf.chain = s->chain; kf.step = st.step_id;
+      const KeepRange kr{6, 6 * (x.it + 1), 6, 0};
+      if (ctx->mlp_dropout == MLP_DROPOUT_DEFAULT) {
+        kf.keep = keep; kf.n3 = n3; kf.kr = kr;
+        kf.seed = s->seed; kf.chain = s->chain; kf.step = st.step_id;
+      } else {                                                  // k_fwdr's rows hold the default law: a launch of its own
+        const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);
+        hipLaunchKernelGGL(k_mlp_keep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, keep, n3, kr,
+                           s->seed, s->chain, st.step_id, ctx->mlp_keep);
+      }
     }
     HMCX_HIP(ctx, mlp_fwdr<T>(net, fa, na, &kf));
     HMCX_HIP(ctx, mlp_ga1_batch<T>(net, x.ga, x.nga));
@@ -1515,7 +1524,7 @@ struct MlpSghmc {
       const KeepRange kr{6 * st.n - 6, 6, 6 * st.n - 6, 0};
       const size_t items = (size_t)kr.nf * ((n3 + 63) / 64);
       hipLaunchKernelGGL(k_mlp_keep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, keep, n3, kr,
-                         s->seed, s->chain, st.step_id);
+                         s->seed, s->chain, st.step_id, ctx->mlp_keep);
     }
     return quad_ok(net, x.ss) ? &MlpSghmc::iter_quad : &MlpSghmc::iter_chunked;
   }

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_mlp_sgld_chains(MlpSgld<T> a, SgldStrid
     } else if (a.masks) {
       const size_t g = (lb - 1) * 256 + threadIdx.x;
       T* const masks = a.masks + (size_t)c * cs.masks;
-      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(masks, a.n3, a.seed, chain, a.mstep, a.slot, (int)g);
+      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.law, masks, a.n3, a.seed, chain, a.mstep, a.slot, (int)g);
     }
     return;
   }
@@ -332,6 +332,7 @@ int mlp_sgld_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sgld_chains_args* s) {
       L.net[c] = &cn[c]; L.q[c] = q[c]; L.g[c] = gc[c]; L.lpart[c] = lpart + (size_t)c * nlb;
     }
     MlpSgld<T> k{};
+    k.law = drop_law<T>(ctx);
     for (int v = 0; v < 6; ++v) {
       k.vt.q[v] = q[0][v];
       k.vt.p[v] = s->variant == 1 ? (void*)((T*)s->mom.p[v] + (size_t)c0 * (size_t)net.nvar(v)) : nullptr;

@@ -25,6 +25,7 @@ template <typename T> struct HmcGroup {
   double* part;
   T* mA; T* mB; int64_t mstride; int n3;
   uint64_t seed; uint32_t chain, step;   // chain: Philox chain of the group's first chain
+  DropLaw<T> law;                        // of the group's Philox masks
 };
 
 // Step start, every chain of the group (grid NPART × (6 + mask rows) × chains): row v < 6 draws the momentum of
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void k_hmc_start(HmcStart<T> a) {
     if (!a.draw_masks[ci]) return;
     const size_t g = ((size_t)(blockIdx.y - 6) * NPART + blockIdx.x) * 256 + threadIdx.x;
     if (g * 64 < (size_t)a.gr.n3)
-      mlp_masks_group<T>(a.gr.mA + ci * a.gr.mstride, a.gr.n3, a.gr.seed, a.gr.chain + (uint32_t)ci, a.gr.step,
+      mlp_masks_group<T>(a.gr.law, a.gr.mA + ci * a.gr.mstride, a.gr.n3, a.gr.seed, a.gr.chain + (uint32_t)ci, a.gr.step,
                          MASK_SLOT0, (int)g);
     return;
   }
@@ -109,6 +110,7 @@ template <typename T> struct HmcKicks {
   int64_t pstride; int nparts;
   T* masks; int64_t mstride; int n3;  // masks null: no draw; else where has_nv, the next evaluation's slot
   uint64_t seed; uint32_t chain, step, slot;
+  DropLaw<T> law;
 };
 template <typename T>
 __global__ __launch_bounds__(256) void k_hmc_kicks(HmcKicks<T> k) {
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(256) void k_hmc_kicks(HmcKicks<T> k) {
   } else if (k.masks && k.has_nv[blockIdx.z]) {
     T* const m = k.masks + ci * k.mstride;
     for (int64_t g = i0; 64 * g < k.n3; g += st)
-      mlp_masks_group<T>(m, k.n3, k.seed, k.chain + (uint32_t)ci, k.step, k.slot, (int)g);
+      mlp_masks_group<T>(k.law, m, k.n3, k.seed, k.chain + (uint32_t)ci, k.step, k.slot, (int)g);
   }
 }
 
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(256) void k_hmc_ends(HmcEnds<T> a) {
     const int second = g >= (size_t)a.ngroups;
     if (second) g -= (size_t)a.ngroups;
     if (g >= (size_t)a.ngroups) return;
-    mlp_masks_group<T>((second ? a.gr.mB : a.gr.mA) + ci * a.gr.mstride, a.gr.n3, a.gr.seed,
+    mlp_masks_group<T>(a.gr.law, (second ? a.gr.mB : a.gr.mA) + ci * a.gr.mstride, a.gr.n3, a.gr.seed,
                        a.gr.chain + (uint32_t)ci, a.gr.step, a.slot0[ci] + (uint32_t)second, (int)g);
     return;
   }
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(256) void k_hmc_commit(HmcCommit<T> a) {
     if (!a.draw_masks) return;
     const size_t g = ((size_t)(blockIdx.y - 6) * NPART + blockIdx.x) * 256 + threadIdx.x;
     if (g * 64 < (size_t)a.gr.n3)
-      mlp_masks_group<T>(a.gr.mA + ci * a.gr.mstride, a.gr.n3, a.gr.seed, a.gr.chain + (uint32_t)ci, a.gr.step,
+      mlp_masks_group<T>(a.gr.law, a.gr.mA + ci * a.gr.mstride, a.gr.n3, a.gr.seed, a.gr.chain + (uint32_t)ci, a.gr.step,
                          a.slot[ci], (int)g);
     return;
   }
@@ -353,7 +355,7 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
     }
     grp.noise_layout(o, gr.e0);
     gr.part = part; gr.mA = mA; gr.mB = mB; gr.mstride = (int64_t)mstride; gr.n3 = n3;
-    gr.seed = s->seed; gr.chain = s->chain0 + (uint32_t)c0;
+    gr.seed = s->seed; gr.chain = s->chain0 + (uint32_t)c0; gr.law = drop_law<T>(ctx);
     // a forward of the listed chains (group indices) at q' or q under forward number f[ci] of the step
     ChainList<T> L{};
     auto list = [&](const int* idx, int n, bool proposal, const int64_t* f, const T* scr, double* lp, size_t sc) {
@@ -421,7 +423,7 @@ int mlp_hmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_hmc_chains_args* s) {
         k.part_v = any_nv ? grp.part_of(cn[0], vn) : nullptr;
         k.pstride = pstride; k.nparts = nlb;
         const bool kmasks = philox && any_nv;
-        k.masks = kmasks ? mA : nullptr; k.mstride = (int64_t)mstride; k.n3 = n3;
+        k.masks = kmasks ? mA : nullptr; k.law = gr.law; k.mstride = (int64_t)mstride; k.n3 = n3;
         k.seed = s->seed; k.chain = gr.chain; k.step = gr.step;
         k.slot = MASK_SLOT0 + (uint32_t)(e + 1);
         int64_t n = 0;
@@ -506,6 +508,7 @@ template <typename T> struct SghmcUpd {
   uint32_t zslot, e0_u;
   T* masks; int64_t mstride; int n3;  // masks null: no draw; else where has_nv, the next evaluation's slot
   uint64_t seed; uint32_t chain, step, slot;
+  DropLaw<T> law;
 };
 template <typename T>
 __global__ __launch_bounds__(256) void k_sghmc_upd(SghmcUpd<T> k) {
@@ -541,7 +544,7 @@ __global__ __launch_bounds__(256) void k_sghmc_upd(SghmcUpd<T> k) {
   } else if (k.masks && k.has_nv[blockIdx.z]) {
     T* const m = k.masks + ci * k.mstride;
     for (int64_t g = i0; 64 * g < k.n3; g += st)
-      mlp_masks_group<T>(m, k.n3, k.seed, k.chain + (uint32_t)ci, k.step, k.slot, (int)g);
+      mlp_masks_group<T>(k.law, m, k.n3, k.seed, k.chain + (uint32_t)ci, k.step, k.slot, (int)g);
   }
 }
 
@@ -608,7 +611,7 @@ int mlp_sghmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_chains_args* s) {
     }
     grp.noise_layout(o, gr.e0);
     gr.part = part; gr.mA = mA; gr.mB = mB; gr.mstride = (int64_t)mstride; gr.n3 = n3;
-    gr.seed = s->seed; gr.chain = s->chain0 + (uint32_t)c0;
+    gr.seed = s->seed; gr.chain = s->chain0 + (uint32_t)c0; gr.law = drop_law<T>(ctx);
     // a forward of the listed chains (group indices) at q' or q under forward number f[ci] of the step
     ChainList<T> L{};
     auto list = [&](const int* idx, int n, bool proposal, const int64_t* f, const T* scr, double* lp, size_t sc) {
@@ -684,7 +687,7 @@ int mlp_sghmc_chains_t(hmcx_ctx* ctx, const hmcx_mlp_sghmc_chains_args* s) {
         }
         if (any_nv) { k.p_v = p[vn]; k.q_v = qn[vn]; k.n_v = net.nvar(vn); }
         const bool kmasks = philox && any_nv && e >= 0;        // forward 0's masks are the start launch's
-        k.masks = kmasks ? mA : nullptr;
+        k.masks = kmasks ? mA : nullptr; k.law = gr.law;
         k.slot = MASK_SLOT0 + (uint32_t)(e + 1);
         int64_t n = 1;
         if (vu >= 0) n = std::max<int64_t>(n, net.nvar(vu));

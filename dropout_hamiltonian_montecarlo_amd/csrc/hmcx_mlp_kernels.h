@@ -975,8 +975,8 @@ template <typename T> struct RbFwdArgs {
   RbFwdProb<T> p[FR_MAXP];
   PendSet<T> pend;                       // pending updates: run by the extra plane blockIdx.y == np
   unsigned long long* prof;              // HMCX_FWDR_PROF: FR_NPH s_memrealtime stamps per workgroup
-  // the NEXT iteration's keep flags, drawn by the rows after the problems and the pending plane (kr.nf == 0:
-  // none): they land on the CUs the problems leave free (192 + 32 workgroups on 256 CUs)
+  // the NEXT iteration's keep flags under the default dropout ratio, drawn by the rows after the problems and the
+  // pending plane (kr.nf == 0: none): they land on the CUs the problems leave free (192 + 32 workgroups on 256 CUs)
   uint32_t* keep; int n3; KeepRange kr; uint64_t seed; uint32_t chain, step;
 };
 constexpr int FR_NPH = 8;
@@ -993,7 +993,9 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lg = lane >> 4;
   if ((int)blockIdx.y >= a.np + (a.pend.n > 0 ? 1 : 0)) {         // the next iteration's keep flags
     const int y0 = a.np + (a.pend.n > 0 ? 1 : 0);
-    keep_flags(a.keep, a.n3, a.kr, a.seed, a.chain, a.step,
+    // the default ratio's law as constants: a law in scalar registers cost this kernel four more spilled SGPRs, so
+    // under any other ratio the host leaves these rows out (kr.nf == 0) and draws the flags with k_mlp_keep
+    keep_flags(KeepLawDefault{}, a.keep, a.n3, a.kr, a.seed, a.chain, a.step,
                ((size_t)((int)blockIdx.y - y0) * gridDim.x + blockIdx.x) * blockDim.x + tid);
     return;
   }
@@ -1292,14 +1294,14 @@ __global__ __launch_bounds__(FR_NW * 64) void k_fwdr(RbFwdArgs<T> a) {
   stamp(7);
 }
 
-// Mask values of one forward (the API twin of the sampler's keep flags: same groups, value = keep·(1/0.9)).
+// Mask values of one forward (the API twin of the sampler's keep flags: same groups, value = keep·law.scale).
 // Thread g: group g (64 elements), written as 16-byte vectors.
 template <typename T>
-__device__ inline void mlp_masks_group(T* masks, int n3, uint64_t seed, uint32_t chain, uint32_t step, uint32_t slot,
-                                       int g) {
+__device__ inline void mlp_masks_group(const DropLaw<T>& law, T* masks, int n3, uint64_t seed, uint32_t chain, uint32_t step,
+                                       uint32_t slot, int g) {
   if (64 * g >= n3) return;
-  const KeepGroup k = keep_group(seed, (uint32_t)g, slot, step, chain);
-  const T scale = (T)(1.0 / 0.9);
+  const KeepGroup k = keep_group(law.keep, seed, (uint32_t)g, slot, step, chain);
+  const T scale = law.scale;
   constexpr int V = 16 / sizeof(T);
   typedef T tv __attribute__((ext_vector_type(V)));
   const int e0 = 64 * g, n = min(64, n3 - e0);
@@ -1317,8 +1319,8 @@ __device__ inline void mlp_masks_group(T* masks, int n3, uint64_t seed, uint32_t
   }
 }
 template <typename T>
-__global__ void k_mlp_masks(T* masks, int n3, uint64_t seed, uint32_t chain, uint32_t step, uint32_t slot) {
-  mlp_masks_group<T>(masks, n3, seed, chain, step, slot, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+__global__ void k_mlp_masks(DropLaw<T> law, T* masks, int n3, uint64_t seed, uint32_t chain, uint32_t step, uint32_t slot) {
+  mlp_masks_group<T>(law, masks, n3, seed, chain, step, slot, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // The kicks and the drift between two gradient calls of the full-batch trajectory in one launch
@@ -1332,6 +1334,7 @@ template <typename T> struct MlpKicks {
   T* pu; const T* gu; int64_t nu; T eu;
   T* pv; const T* gv; T* qv; int64_t nv; T hv, ev;
   T* masks; int n3; uint64_t seed; uint32_t chain, step, slot;   // masks null: no draw
+  DropLaw<T> law;
   PendSet<T> ps;
 };
 template <typename T> __device__ inline int pend_of(const PendSet<T>& ps, const T* g) {
@@ -1362,7 +1365,7 @@ __global__ __launch_bounds__(256) void k_mlp_kicks(MlpKicks<T> k) {
       k.qv[i] = k.qv[i] + aq;
     }
   } else if (k.masks) {
-    for (int64_t g = i0; 64 * g < k.n3; g += st) mlp_masks_group<T>(k.masks, k.n3, k.seed, k.chain, k.step, k.slot, (int)g);
+    for (int64_t g = i0; 64 * g < k.n3; g += st) mlp_masks_group<T>(k.law, k.masks, k.n3, k.seed, k.chain, k.step, k.slot, (int)g);
   }
 }
 // p = −p of the six variables (hmc.py:55-56, k_axpy's p − 2·p), one launch (row = variable)
@@ -1451,12 +1454,13 @@ __global__ __launch_bounds__(256) void k_mlp_init(VarTab vt, T eps, int drift, i
 template <typename T>
 __global__ __launch_bounds__(256) void k_mlp_start(VarTab vt, T eps, int drift, int noise_mode, const double* noise,
                                                    uint64_t seed, uint32_t chain, uint32_t step, double* part,
-                                                   const int32_t* prev_acc, uint32_t* keep, int n3, KeepRange kr) {
+                                                   const int32_t* prev_acc, uint32_t* keep, int n3, KeepRange kr,
+                                                   KeepLaw law) {
   if (blockIdx.y < 6) {
     init_block<T>(vt, eps, drift, noise_mode, noise, seed, chain, step, part, (int)blockIdx.y, (int)blockIdx.x,
                   prev_acc);
   } else {
-    keep_flags(keep, n3, kr, seed, chain, step, ((size_t)(blockIdx.y - 6) * NPART + blockIdx.x) * 256 + threadIdx.x);
+    keep_flags(law, keep, n3, kr, seed, chain, step, ((size_t)(blockIdx.y - 6) * NPART + blockIdx.x) * 256 + threadIdx.x);
   }
 }
 

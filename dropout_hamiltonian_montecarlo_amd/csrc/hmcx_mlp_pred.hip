@@ -174,6 +174,7 @@ template <typename T> struct PredFused {
   uint64_t seed; uint32_t chain, step, slot0;                  // MK_PHILOX
   double* gmean; double* gH; double* gpy;                      // group partials [G][N][n_out], [G][N], [G][N]
   double* nll_part; int32_t* corr_part;                        // [D][row blocks], null without labels
+  DropLaw<T> law;                                              // MK_PHILOX_LAW; last: the fields before it keep their offsets
 };
 
 // LDS layout of k_pred_fused (bytes): X tile, h1 tile, d3 tile, per-wave logit partials, keep words, row scratch.
@@ -275,6 +276,18 @@ __device__ inline double pf_sum16(double v) {
   return v;
 }
 
+// k_pred_fused's keep-flag draw as calls, not inlined: the kernel sits at its register limit (256 VGPRs in float64)
+// and the inlined draw costs it spills and scratch.  The default ratio's law is compiled in (MK_PHILOX), any other
+// arrives by value (MK_PHILOX_LAW).
+__device__ __noinline__ KeepGroup pred_keep_group_default(uint64_t seed, uint32_t G, uint32_t slot, uint32_t step,
+                                                          uint32_t chain) {
+  return keep_group(KeepLawDefault{}, seed, G, slot, step, chain);
+}
+__device__ __noinline__ KeepGroup pred_keep_group_law(KeepLaw law, uint64_t seed, uint32_t G, uint32_t slot,
+                                                      uint32_t step, uint32_t chain) {
+  return keep_group(law, seed, G, slot, step, chain);
+}
+
 template <typename T, int MK>
 __global__ __launch_bounds__(PF_NT) void k_pred_fused(PredFused<T> a) {
   using Mf = mfma16<T>;
@@ -295,7 +308,10 @@ __global__ __launch_bounds__(PF_NT) void k_pred_fused(PredFused<T> a) {
   const int n0 = 32 * wave;
   const bool wact = n0 < nm;                                   // this wave has columns (n_mid % 32 == 0: all 32)
   const bool rok = m0 + lr < N;                                // the row of this lane's accumulator column
-  const T scale = (T)(1.0 / 0.9);
+  // the keep law: the default ratio's as constants (MK_PHILOX), any other ratio's from the argument block
+  // (MK_PHILOX_LAW)
+  constexpr bool PHILOX = MK == MK_PHILOX || MK == MK_PHILOX_LAW;
+  const T scale = MK == MK_PHILOX_LAW ? a.law.scale : (T)(1.0 / (1.0 - MLP_DROPOUT_DEFAULT));
 
   // the row block of X, once: rows past N and columns past n_in are zero
   for (int e = tid; e < PF_ROWS * a.xk; e += PF_NT) {
@@ -312,7 +328,7 @@ __global__ __launch_bounds__(PF_NT) void k_pred_fused(PredFused<T> a) {
   auto mask = [&](int which, int d, int n) -> T {
     if constexpr (MK == MK_VALS) {
       return rok ? a.masks[((size_t)d * 3 + which) * mn + (size_t)(m0 + lr) * nm + n] : T(1);
-    } else if constexpr (MK == MK_PHILOX) {
+    } else if constexpr (PHILOX) {
       const size_t e = elo[which] + (size_t)lr * nm + n;
       const uint32_t wd = kw[which * PF_KWN + (int)((e >> 5) - ((elo[which] >> 6) << 1))];
       return ((wd >> (e & 31)) & 1u) ? scale : T(0);
@@ -336,10 +352,12 @@ __global__ __launch_bounds__(PF_NT) void k_pred_fused(PredFused<T> a) {
     const T* b2 = a.p[3] + (size_t)s * nm;
     const T* W3 = a.p[4] + (size_t)s * No * nm;
     const T* b3 = a.p[5] + (size_t)s * No;
-    if constexpr (MK == MK_PHILOX) {                           // the draw's keep flags of this row block
+    if constexpr (PHILOX) {                                    // the draw's keep flags of this row block
       if (tid < 3 * ngr) {
         const int w = tid / ngr, gi = tid - w * ngr;
-        const KeepGroup k = keep_group(a.seed, (uint32_t)(elo[w] >> 6) + (uint32_t)gi, a.slot0 + (uint32_t)d, a.step, a.chain);
+        const uint32_t G = (uint32_t)(elo[w] >> 6) + (uint32_t)gi, slot = a.slot0 + (uint32_t)d;
+        const KeepGroup k = MK == MK_PHILOX_LAW ? pred_keep_group_law(a.law.keep, a.seed, G, slot, a.step, a.chain)
+                                                : pred_keep_group_default(a.seed, G, slot, a.step, a.chain);
         kw[w * PF_KWN + 2 * gi] = k.lo;
         kw[w * PF_KWN + 2 * gi + 1] = k.hi;
       }
@@ -582,7 +600,9 @@ int mlp_predictive_t(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
   } else {
     const int nrb = (N + PF_ROWS - 1) / PF_ROWS;
     const PfLds L = pf_lds(a->n_in, nm, sizeof(T));
-    const void* kfn = a->mask_mode == HMCX_MLP_MASKS_PHILOX ? (const void*)k_pred_fused<T, MK_PHILOX>
+    const bool any_law = ctx->mlp_dropout != MLP_DROPOUT_DEFAULT;
+    const void* kfn = a->mask_mode == HMCX_MLP_MASKS_PHILOX
+                          ? (any_law ? (const void*)k_pred_fused<T, MK_PHILOX_LAW> : (const void*)k_pred_fused<T, MK_PHILOX>)
                       : a->mask_mode == HMCX_MLP_MASKS_FIXED ? (const void*)k_pred_fused<T, MK_VALS>
                                                              : (const void*)k_pred_fused<T, MK_NONE>;
     int per_cu = 0;
@@ -613,11 +633,13 @@ int mlp_predictive_t(hmcx_ctx* ctx, const hmcx_mlp_predictive_args* a) {
     f.X = (const T*)a->X; f.y = a->y;
     for (int v = 0; v < 6; ++v) f.p[v] = (const T*)a->par.p[v];
     f.masks = (const T*)a->masks;
-    f.seed = a->seed; f.chain = a->chain; f.step = a->step; f.slot0 = a->slot0;
+    f.seed = a->seed; f.chain = a->chain; f.step = a->step; f.slot0 = a->slot0; f.law = drop_law<T>(ctx);
     f.gmean = gm; f.gH = gH; f.gpy = gpy; f.nll_part = np; f.corr_part = cp;
     const dim3 grid((unsigned)nrb, (unsigned)G), block(PF_NT);
     if ((rc = timing_begin(ctx, ctx->stream))) return rc;
-    if (a->mask_mode == HMCX_MLP_MASKS_PHILOX)
+    if (a->mask_mode == HMCX_MLP_MASKS_PHILOX && any_law)
+      hipLaunchKernelGGL((k_pred_fused<T, MK_PHILOX_LAW>), grid, block, L.total, ctx->stream, f);
+    else if (a->mask_mode == HMCX_MLP_MASKS_PHILOX)
       hipLaunchKernelGGL((k_pred_fused<T, MK_PHILOX>), grid, block, L.total, ctx->stream, f);
     else if (a->mask_mode == HMCX_MLP_MASKS_FIXED)
       hipLaunchKernelGGL((k_pred_fused<T, MK_VALS>), grid, block, L.total, ctx->stream, f);

@@ -21,6 +21,7 @@ template <typename T> struct MlpSgd {
   double* part;
   const double* lpart; int nlb, B; double* out_loss;               // out_loss null: no loss
   T* masks; int n3; uint64_t seed; uint32_t chain, step, slot;     // masks null: no draw
+  DropLaw<T> law;
 };
 template <typename T>
 __global__ __launch_bounds__(256) void k_mlp_sgd(MlpSgd<T> a) {
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void k_mlp_sgd(MlpSgd<T> a) {
       }
     } else if (a.masks) {
       const size_t g = (lb - 1) * 256 + threadIdx.x;
-      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.masks, a.n3, a.seed, a.chain, a.step, a.slot, (int)g);
+      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.law, a.masks, a.n3, a.seed, a.chain, a.step, a.slot, (int)g);
     }
     return;
   }
@@ -102,6 +103,7 @@ template <typename T> struct MlpSgld {
   double* part;
   const double* lpart; int nlb, B; double* out_loss;               // out_loss null: no loss
   T* masks; int n3; uint32_t mstep, slot;                          // masks null: no draw
+  DropLaw<T> law;
 };
 // The one-chain kernel: k_mlp_sgld_chains's statements (hmcx_mlp_chains.hip) without the chain offsets (sharing
 // one body cost it 2 – 3 SGPRs); keep the two in step.
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void k_mlp_sgld(MlpSgld<T> a) {
       }
     } else if (a.masks) {
       const size_t g = (lb - 1) * 256 + threadIdx.x;
-      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.masks, a.n3, a.seed, a.chain, a.mstep, a.slot, (int)g);
+      if (g * 64 < (size_t)a.n3) mlp_masks_group<T>(a.law, a.masks, a.n3, a.seed, a.chain, a.mstep, a.slot, (int)g);
     }
     return;
   }

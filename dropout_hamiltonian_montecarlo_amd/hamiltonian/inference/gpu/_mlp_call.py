@@ -1,13 +1,16 @@
 """What the callers of the dropout MLP's device entry points (sgd, sgld, sghmc, hmc_multicore) share: the
 resolution of the ``masks`` argument and ``mask_provider`` into a mask mode with host buffers, the six parameter
-pointers of an argument block, and negative_log_posterior from an evaluation's device outputs.  Nothing here
-touches a device: the callers upload what ``mask_plan`` returns."""
+pointers of an argument block, negative_log_posterior from an evaluation's device outputs, and the context a call
+uses (``mlp_context``: the model's device context with the model's dropout ratio set, models/gpu/mlp.py's helper —
+every sampler call that reaches an hmcx_mlp_* entry takes its context from it).  Nothing else here touches a device:
+the callers upload what ``mask_plan`` returns.  A provider's masks are used as given: under a model whose dropout
+ratio is not the default they should carry 1/(1 − dropout) where they keep."""
 import numpy as np
 
 from dropout_hamiltonian_montecarlo_amd import _native as nat
 from dropout_hamiltonian_montecarlo_amd._native import HmcxError
 
-from ...models.gpu.mlp import MLP_PARAM_NAMES
+from ...models.gpu.mlp import MLP_PARAM_NAMES, mlp_context  # noqa: F401  (mlp_context: the callers' context)
 
 
 def masks_off(masks_arg):

@@ -159,7 +159,7 @@ class hmc_multicore(hmc):
             if self.keep_momentum:
                 moms = [torch.empty((C, n_steps) + m.shapes[k], dtype=dt, device=dev) for k in MLP_PARAM_NAMES]
                 _mlp_call.fill_params(a.out_mom, moms)
-        ctx = nat.context(dev)
+        ctx = _mlp_call.mlp_context(self.model)
         ctx.check(ctx.lib.hmcx_mlp_hmc_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_hmc_chains_run")
         self.global_step += n_steps
         f = out_f.cpu().numpy()

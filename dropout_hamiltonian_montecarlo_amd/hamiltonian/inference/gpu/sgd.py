@@ -162,7 +162,7 @@ class sgd:
         _mlp_call.fill_params(a.par, par)
         _mlp_call.fill_params(a.mom, mom)
         a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
-        ctx = nat.context(dev)
+        ctx = _mlp_call.mlp_context(self.model)
         if n_steps:
             ctx.check(ctx.lib.hmcx_mlp_sgd_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgd_run")
         self.global_step += n_steps

@@ -519,7 +519,7 @@ class sghmc(sgmcmc):
             a.want_draw = want_draw.ctypes.data_as(nat.c_u8p)
             _mlp_call.fill_params(a.draws, {k: draw[k][:, d0:] for k in draw})
             a.draw_stride = draw[_mlp_call.MLP_PARAM_NAMES[0]].shape[1]
-        ctx = nat.context(dev)
+        ctx = _mlp_call.mlp_context(self.model)
         ctx.check(ctx.lib.hmcx_mlp_sghmc_chains_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sghmc_chains_run")
         self.global_step += n_steps
         h = {k: v.cpu().numpy() for k, v in outs.items()}               # waits for the call
@@ -593,7 +593,7 @@ class sghmc(sgmcmc):
         a.out_A, a.out_accepted = ptr(outs['A']), ptr(out_acc)
         a.out_loss, a.out_nlp, a.out_E = ptr(outs['loss']), ptr(outs['nlp']), ptr(outs['E'])
         a.out_abort = ptr(out_abort)
-        ctx = nat.context(dev)
+        ctx = _mlp_call.mlp_context(self.model)
         # the state before the call: a call whose fused exchange timed out leaves it invalid (below)
         saved = [state[k].clone() for k in MLP_PARAM_NAMES] if ctx.mlp_fuse else None
         ctx.check(ctx.lib.hmcx_mlp_sghmc_run(ctx.h, a), "hmcx_mlp_sghmc_run")

@@ -325,7 +325,7 @@ class sgld(sgmcmc):
             if C > 1:
                 a.draw_stride = draw[_mlp_call.MLP_PARAM_NAMES[0]].shape[1]
         a.out_loss, a.out_eval_loss, a.out_eval_sumsq = ptr(out_loss), ptr(ev_loss), ptr(ev_ss)
-        ctx = nat.context(dev)
+        ctx = _mlp_call.mlp_context(self.model)
         if C == 1:
             ctx.check(ctx.lib.hmcx_mlp_sgld_run(ctx.h, ctypes.byref(a)), "hmcx_mlp_sgld_run")
         else:

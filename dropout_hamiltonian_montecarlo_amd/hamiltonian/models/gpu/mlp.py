@@ -15,6 +15,13 @@ Dropout.  Chainer draws fresh masks on every forward (train mode).  Here ``masks
 on the device from Philox (hmcx_mlp_masks, keyed by the model's seed and a call counter);
 ``masks='off'`` disables dropout; an explicit ``masks=[m1, m2, m3]`` (each [B, n_mid]) injects
 them — the parity mode against oracle/models.py::mlp.
+
+The dropout ratio is the model's: ``mlp(..., dropout=r)`` (default 0.1, the reference's ``F.dropout(ratio=.1)``)
+drops an element with probability r and gives a kept one the value 1/(1 − r) in every Philox mask drawn for this
+model — grad, the samplers' device calls, predict, predict_stochastic and posterior_predictive alike.  Injected
+masks (``masks=[...]``, ``mask_provider``) are used as given: with a ratio other than the default they should carry
+1/(1 − dropout) where they keep.  The contexts of a device are shared by its models, so every call first makes the
+context's ratio the calling model's (``mlp_context``).
 """
 import collections
 import ctypes
@@ -24,7 +31,8 @@ import torch
 
 from dropout_hamiltonian_montecarlo_amd._native import (HmcxError, MlpLeapfrogArgs, MlpParams, MlpPredictiveArgs,
                                                         MLP_MASK_SLOT0, MLP_MASKS_FIXED, MLP_MASKS_NONE,
-                                                        MLP_MASKS_PHILOX, context, dtype_code, ptr)
+                                                        MLP_MASKS_PHILOX, MLP_DROPOUT_DEFAULT, context, dtype_code,
+                                                        mlp_dropout_threshold, ptr)
 
 from .softmax import _batch, as_device
 
@@ -52,10 +60,22 @@ def init_params(shape, seed=0):
     return out
 
 
+def mlp_context(model):
+    """The context of the model's device with the model's dropout ratio set: what every call that reaches an
+    hmcx_mlp_* entry on behalf of ``model`` uses (here and, through inference/gpu/_mlp_call.py, in the samplers).
+    A model without the attribute (a stand-in) runs at the default."""
+    ctx = context(model.device)
+    ctx.set_mlp_dropout(getattr(model, 'dropout', MLP_DROPOUT_DEFAULT))
+    return ctx
+
+
 class mlp:
     _hmcx_model = 'mlp'
 
-    def __init__(self, _hyper, n_in, n_mid_units, n_out, dtype=torch.float32, device=None, seed=0):
+    def __init__(self, _hyper, n_in, n_mid_units, n_out, dtype=torch.float32, device=None, seed=0,
+                 dropout=MLP_DROPOUT_DEFAULT):
+        mlp_dropout_threshold(dropout)                 # ValueError for an invalid ratio, before any device is touched
+        self.dropout = float(dropout)
         self.hyper = _hyper
         self.alpha = float(np.asarray(_hyper['alpha']))
         self.n_in, self.n_mid, self.n_out = int(n_in), int(n_mid_units), int(n_out)
@@ -107,7 +127,7 @@ class mlp:
         out = torch.empty((3, B, self.n_mid), dtype=self.dtype, device=self.device)
         slot = (MLP_MASK_SLOT0 + self._mask_calls) & 0xFFFFFFFF
         self._mask_calls += 1
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_masks(ctx.h, self.code, B, self.n_mid, self.seed, 0, 0xFFFFFFFF, slot, ptr(out)),
                   "hmcx_mlp_masks")
         return out
@@ -134,7 +154,7 @@ class mlp:
         gp = MlpParams()
         for i, g in enumerate(gs):
             gp.p[i] = g.data_ptr()
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_grad(ctx.h, self.code, ptr(X), ptr(y), B, self.n_in, self.n_mid, self.n_out, mp,
                                         ptr(m), self.alpha, gp, None), "hmcx_mlp_grad")
         return {k: g for k, g in zip(MLP_PARAM_NAMES, gs)}
@@ -183,7 +203,7 @@ class mlp:
             keep = self._masks(masks, B)
             a.mask_mode = MLP_MASKS_NONE if keep is None else MLP_MASKS_FIXED
             a.masks = None if keep is None else keep.data_ptr()
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_hmc_leapfrog(ctx.h, ctypes.byref(a)), "hmcx_mlp_hmc_leapfrog")
         del keep                                        # stream-ordered: the allocator reuses it after the launches
         return gs
@@ -194,7 +214,7 @@ class mlp:
         _, mp = self._params(par)
         m = self._masks(masks, B)
         out = torch.empty(1, dtype=torch.float64, device=self.device)
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_loss(ctx.h, self.code, ptr(X), ptr(y), B, self.n_in, self.n_mid, self.n_out, mp,
                                         ptr(m), ptr(out), None), "hmcx_mlp_loss")
         return out
@@ -204,7 +224,7 @@ class mlp:
 
     def log_prior(self, par, **args):                                     # mlp.py:40-45
         """−Σ_var ½·alpha·Σθ²/dim, with Σθ² a float64 device reduction (hmcx_sumsq)."""
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ss = torch.empty(len(par), dtype=torch.float64, device=self.device)
         keep = []
         for i, var in enumerate(par.keys()):
@@ -229,7 +249,7 @@ class mlp:
         B = X.shape[0]
         _, mp = self._params(par)
         m = self._masks(masks, B)
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_loss(ctx.h, self.code, ptr(X), ptr(y), B, self.n_in, self.n_mid, self.n_out, mp,
                                         ptr(m), ptr(out[0:1]), None), "hmcx_mlp_loss")
         keep = [m]
@@ -257,7 +277,7 @@ class mlp:
         _, mp = self._params(par)
         m = self._masks(masks, B)
         z = torch.empty((B, self.n_out), dtype=self.dtype, device=self.device)
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_loss(ctx.h, self.code, ptr(X), None, B, self.n_in, self.n_mid, self.n_out, mp,
                                         ptr(m), None, ptr(z)), "hmcx_mlp_loss")
         return z
@@ -354,7 +374,7 @@ class mlp:
         if yt is not None:
             lppd, nll, corr = torch.empty(N, **f64), torch.empty(D, **f64), torch.empty(D, **i32)
             a.out_lppd, a.out_draw_nll, a.out_draw_correct = lppd.data_ptr(), nll.data_ptr(), corr.data_ptr()
-        ctx = context(self.device)
+        ctx = mlp_context(self)
         ctx.check(ctx.lib.hmcx_mlp_predictive(ctx.h, ctypes.byref(a)), "hmcx_mlp_predictive")
         host = [None if t is None else t.cpu().numpy() for t in (mean, pred, ent, eent, lppd, nll, corr)]
         del ts, m, yt, X                                  # read by the launches the copies above waited for

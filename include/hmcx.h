@@ -511,15 +511,17 @@ int hmcx_axpy(hmcx_ctx* ctx, int dtype, int mode, int64_t n, double a, const voi
  * relu(dropout) -> dropout -> l3) and :47-82 (grad / log_likelihood / negative_log_posterior)
  * without Chainer.  Parameters in Chainer's layout, L.Linear W = [out][in]:
  *   W1 [n_mid][n_in], b1 [n_mid], W2 [n_mid][n_mid], b2 [n_mid], W3 [n_out][n_mid], b3 [n_out].
- * Dropout (mlp.py:29-31, ratio 0.1, train mode): mask = (u >= 0.1) / 0.9 for the three [B][n_mid]
- * activations of every forward.  mask_mode BUFFER: masks[...] holds them (3·B·n_mid values per
- * forward, dtype); PHILOX: u = Philox(seed, chain, step, slot = forward index, element).       */
+ * Dropout (mlp.py:29-31, train mode): mask = (u >= ratio) / (1 − ratio) for the three [B][n_mid]
+ * activations of every forward, ratio the context's (hmcx_set_mlp_dropout; 0.1 by default, the
+ * reference's).  mask_mode BUFFER: masks[...] holds them (3·B·n_mid values per forward, dtype) and is
+ * used as given, whatever the ratio; PHILOX: u = Philox(seed, chain, step, slot = forward index, element). */
 typedef struct hmcx_mlp_params {
   void* p[6];              /* W1, b1, W2, b2, W3, b3 (device, dtype) */
 } hmcx_mlp_params;
 
-/* Philox dropout masks of one forward: out [3][B][n_mid] (dtype) = (u >= 0.1)/0.9 with
- * u = Philox(seed, chain, step, slot, element) — the masks hmcx_mlp_sghmc_run draws (PHILOX). */
+/* Philox dropout masks of one forward: out [3][B][n_mid] (dtype) = (u >= ratio) / (1 − ratio) with
+ * u = Philox(seed, chain, step, slot, element) and the context's ratio (hmcx_set_mlp_dropout) — the masks
+ * every PHILOX mode of the MLP entries below draws. */
 int hmcx_mlp_masks(hmcx_ctx* ctx, int dtype, int B, int n_mid, uint64_t seed, uint32_t chain, uint32_t step,
                    uint32_t slot, void* out);
 
@@ -1037,6 +1039,15 @@ int hmcx_input_masks(hmcx_ctx* ctx, int N, int D, double keep_p, uint64_t seed, 
 /* on = 0: hmcx_mlp_sghmc_run stops fusing layer 2 and layer 3 into one launch (no cross-workgroup
  * exchange; one more launch per forward) — the recovery path after out_abort; on = 1 restores it. */
 int hmcx_set_mlp_fuse(hmcx_ctx* ctx, int on);
+/* The dropout ratio of every Philox mask the context draws from then on (default 0.1): hmcx_mlp_masks,
+ * hmcx_mlp_hmc_leapfrog, hmcx_mlp_sghmc_run, hmcx_mlp_sgd_run, hmcx_mlp_sgld_run, the three *_chains_run entries
+ * and hmcx_mlp_predictive in their PHILOX mask modes.  An element with 24-bit uniform x is kept iff
+ * x >= ceil(ratio · 2^24) and then has the value (dtype)(1 / (1 − ratio)); at 0.1 that is x >= 0x19999A and
+ * (dtype)(1 / 0.9).  Valid iff 0 <= ratio and ceil(ratio · 2^24) < 2^24; anything else (negative, NaN, 1 and above)
+ * returns HMCX_EINVAL with a message and leaves the ratio as it was.  FIXED / BUFFER masks are the caller's values,
+ * untouched; a context shared by models of different ratios sets it before each call. */
+int hmcx_set_mlp_dropout(hmcx_ctx* ctx, double ratio);
+int hmcx_get_mlp_dropout(const hmcx_ctx* ctx, double* ratio);
 /* Wide SGLD (config 5, hmcx_sgld_run with K ≤ 64 or several chains): fused forward + softmax (1, the
  * default) or the three-launch form (0).  A fused call given out_abort stores its verdict there
  * (stream-ordered, no host wait): 1 means a team round timed out and W / b (pW / pb) are invalid —
